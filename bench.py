@@ -4,8 +4,14 @@
 push + proportional sample, double-DQN update with target net, Adam), weak-scaled over N GPUs
 (configs[3]: one RCCL all-reduce of the 520 head gradients + counters per update).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--arenas 65536] [--pool 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--arenas 65536] [--pool 8] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it sets up, runs W warm-up steps, times exactly
+K steps, writes the outputs of the last timed step when --dump-outputs DIR is given (DIR/<name>.npy,
+see dump_outputs; the same arguments give the same inputs on every run) and prints the line (metric,
+value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed step, the configuration
+and the learner's counters). Everything else listed below is measured only with --full.
 
 --gpus N is authoritative (launch_plan): without a launcher (WORLD_SIZE unset) and N > 1 the bench
 starts `torch.distributed.run --nproc-per-node N bench.py ...` as a child before any GPU call and
@@ -13,7 +19,7 @@ exits with its code; WORLD_SIZE != N, or fewer visible GPUs than N, exits 2 with
 
 A step = one vector step: every arena on every rank advances one env step and every rank runs one
 PER update of batch 256. value = total env-steps (all ranks) / max-over-ranks wall time of K steps.
-Rank 0 prints one JSON line. Also reported:
+Rank 0 prints one JSON line. With --full it also reports (--no-cpu-baseline drops the CPU legs):
   roofline      the step's dominant launch, k_learn + its extra blocks (pm_selfplay_learn_act): the
                 single-workgroup double-DQN update (+ Adam + sum-tree refresh) and, on the other CUs,
                 the next vector step's update-independent QNet work on the matrix cores: the
@@ -64,13 +70,13 @@ PEAK_FP32_TFLOPS = 157.3
 INSTR = 20  # after the timed region: one instrumented (timer-armed) step per INSTR production steps
 
 
-def timed_region(one_step, steps, dist, n_events, after=None, at_end=None):
+def timed_region(one_step, steps, dist, n_events, after=None, at_end=None, instrument=True):
     """Time exactly `steps` production steps (barrier + synchronize on both sides, max over ranks),
-    then run steps // INSTR (at least 5) instrumented steps, each after INSTR - 1 production steps,
-    OUTSIDE the timed region (`after()` runs after each, e.g. to read the launch timers): it never
-    counts towards `value`. `at_end()` runs right after the timed region, before any instrumented
-    step (e.g. to read the counters the timed steps left). Returns (seconds, [event tuples], at_end's
-    result)."""
+    then, with `instrument` (--full), run steps // INSTR (at least 5) instrumented steps, each after
+    INSTR - 1 production steps, OUTSIDE the timed region (`after()` runs after each, e.g. to read the
+    launch timers): it never counts towards `value`. `at_end()` runs right after the timed region,
+    before any instrumented step (e.g. to read the counters and outputs the timed steps left).
+    Returns (seconds, [event tuples], at_end's result)."""
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -86,6 +92,8 @@ def timed_region(one_step, steps, dist, n_events, after=None, at_end=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     end = at_end() if at_end is not None else None
+    if not instrument:
+        return dt, [], end
     evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(n_events)) for _ in range(max(5, steps // INSTR))]
     for ev in evs:
         for _ in range(INSTR - 1):
@@ -114,6 +122,72 @@ def pmc_traffic(kernel, profile="r3_pmc.json"):
         except (OSError, KeyError, ValueError):
             continue
     return None
+
+
+DUMP_CAP_BYTES = 60 * 1000 * 1000  # of array files; the directory stays under 64 MB with room to spare
+
+
+def snapshot(tensors):
+    """Host copies of the named device tensors (None entries dropped), taken right after the timed
+    region: what the last timed step left, before anything else runs on the device."""
+    torch.cuda.synchronize()
+    return {k: v.detach().cpu().numpy().copy() for k, v in tensors.items() if v is not None}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs DIR: write `arrays` (name -> numpy array) as DIR/<name>.npy, float32 or float64
+    (float64 sources and 32 / 64-bit integers go to float64, which holds every value this bench
+    produces exactly; everything else to float32). The files may hold DUMP_CAP_BYTES (60 MB, so
+    the directory stays under 64 MB): from the smallest array up, each gets an equal share of what is left; one larger than its share is written as a
+    fixed sample of its rows (leading axis, default_rng(0), ascending: the same rows on every run). Returns {name: [shape, dtype, rows kept of
+    rows]}."""
+    os.makedirs(path, exist_ok=True)
+    left, listing = DUMP_CAP_BYTES, {}
+    todo = sorted(arrays, key=lambda k: (np.asarray(arrays[k]).size, k))  # smallest first: they stay whole
+    for i, name in enumerate(todo):
+        a = np.asarray(arrays[name])
+        wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize >= 4)
+        a = np.ascontiguousarray(a, dtype=np.float64 if wide else np.float32)
+        a = a.reshape(1) if a.ndim == 0 else a
+        rows = a.shape[0]
+        share = left // (len(todo) - i) - 256  # 256: the .npy header
+        if a.nbytes > share:
+            keep = max(1, share // max(a.nbytes // rows, 1))
+            a = a[np.sort(np.random.default_rng(0).choice(rows, size=min(keep, rows), replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes + 256
+        listing[name] = [list(a.shape), str(a.dtype), a.shape[0], rows]
+    return {k: listing[k] for k in arrays}
+
+
+CTRL_DUMPED = ("step", "pos", "size", "train_steps", "frame_idx", "episodes", "epsilon", "max_prio", "last_loss",
+               "status")
+
+
+def dqn_outputs(L, c):
+    """What SelfPlayLearner.step() leaves its caller after the last timed step: the learner's and the
+    target's parameters, Adam's moments, the last update's gradient buffer, sample and IS weights, both
+    players' observations and actions, the env state (arena-major), per-arena bookkeeping, the replay
+    ring with its priorities, and the control block's counters `c` (CTRL_DUMPED order)."""
+    return snapshot({
+        "paramsB": L.paramsB, "paramsT": L.paramsT, "adam_m": L.adam_m, "adam_v": L.adam_v, "grad": L.grad,
+        "sample_idx": L.idx, "sample_isw": L.isw, "obsA": L.obsA, "obsB": L.obsB, "aA": L.aA, "aB": L.aB,
+        "env_f64": L.f64.t(), "env_i32": L.i32.t(), "ep_reward": L.ep_reward, "opp": L.opp,
+        "replay_trans": L.trans, "replay_prios": L.prios,
+        "counters": torch.tensor([float(c[k]) for k in CTRL_DUMPED], dtype=torch.float64)})
+
+
+def rnn_outputs(L, c):
+    """The same for RNNSelfPlayLearner.step(): the DRQN learner's parameters, target, Adam moments,
+    gradient and last batch, modelB's recurrent state, observations, actions, env state and every
+    numeric counter of the control block `c` (sorted by name)."""
+    D = L.learner
+    return snapshot({
+        "params": D.params, "target": D.target, "adam_m": D.adam_m, "adam_v": D.adam_v, "grad": D.grad,
+        "batch_obs": D.obs, "batch_act": D.act, "batch_rew": D.rew, "hB": L.hB, "cB": L.cB,
+        "obsA": L.obsA, "obsB": L.obsB, "aA": L.aA, "aB": L.aB, "env_f64": L.f64.t(), "env_i32": L.i32.t(),
+        "ep_reward": L.ep_reward, "opp": L.opp,
+        "counters": torch.tensor([float(c[k]) for k in sorted(c)], dtype=torch.float64)})
 
 
 def replicas_identical(dist, params):
@@ -479,22 +553,22 @@ def run_rnn(args, dist, rank, world, allreduce):
     torch.cuda.synchronize()
     c0 = L.counters()
     act_t = []
-    dt, evs, c1 = timed_region(one_step, args.steps, dist, 4, lambda: act_t.append(_lib.timer_read(_lib.PM_TIMER_RNN_ACT)),
-                               L.counters)
+
+    def at_end():
+        c = L.counters()
+        return c, (rnn_outputs(L, c) if args.dump_outputs and rank == 0 else None)
+
+    dt, evs, (c1, dumped) = timed_region(one_step, args.steps, dist, 4,
+                                         lambda: act_t.append(_lib.timer_read(_lib.PM_TIMER_RNN_ACT)), at_end,
+                                         instrument=args.full)
     same = replicas_identical(dist, L.learner.params)
-    act_s = sum(act_t) / len(act_t)  # k_rnn_act's own dispatch (pm_timer_*), as rocprofv3 times it
-    env_s = sum(e[1].elapsed_time(e[2]) for e in evs) * 1e-3 / len(evs)  # overlap: env + update
-    upd_s = sum(e[2].elapsed_time(e[3]) for e in evs) * 1e-3 / len(evs)
     c = L.counters()
     shards, shards_ok = shard_proof(dist, rank, world, n, c["step"], c["status"] & 1, args.comm)
     dst = L.learner.stats()
     failed = (c["status"] & 1) != 0 or dst["status"] != 0 or not shards_ok or (dist is not None and not same)
-    drqn = time_drqn_update(L.learner) if world == 1 else None
+    drqn = time_drqn_update(L.learner) if args.full and world == 1 else None
     if rank == 0:
         value = n * world * args.steps / dt
-        fpa = RNN_FLOP_PER_ARENA // 2 if overlap else RNN_FLOP_PER_ARENA  # overlap: modelB's side only
-        achieved = n * fpa / act_s / 1e12
-        env_gbs = n * RNN_ENV_BYTES / env_s / 1e9
         out = {
             "metric": "env-steps/sec (whole node), QNetRNN self-play + DRQN (configs[4])",
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": warm,
@@ -510,33 +584,42 @@ def run_rnn(args, dist, rank, world, allreduce):
                        "parallelism": f"dp{world} (arena shards, 1 all-reduce/update)",
                        "all_reduce": args.comm_used if world > 1 else None, "replicas_identical": same,
                        "shards": shards},
-            "roofline": {"bound": "mfma",
-                         "kernel": "k_rnn_act side B: the overlapped step's act for modelB" if overlap
-                                   else "k_rnn_act (both players)",
-                         "timing": "the launch's own begin/end (hipExtLaunchKernel events, pm_timer_arm) "
-                                   "on instrumented production steps after the timed region",
-                         "compute": "v_mfma_f32_32x32x2_f32 (exact fp32; dense FP32 matrix peak 157.3 TF)",
-                         "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_FP32_TFLOPS, 4),
-                         # modelB's side: 256 blocks x 256 lanes (the overlapped step's only k_rnn_act of
-                         # that grid); the plain step's both-players launch has no committed pass
-                         "traffic": pmc_traffic(f"k_rnn_act@{256 * 256}", "r3_rnn_pmc.json") if overlap and n == 32768 else None,
-                         "avg_us": round(act_s * 1e6, 2), "flop_per_arena": fpa, "n": n},
         }
-        if overlap:
-            out["env_update_us"] = round(env_s * 1e6, 2)  # env + sample + DRQN update, the opponents' act beside
-        else:
-            out["env_roofline"] = {"bound": "hbm", "kernel": "k_rsp_env + k_rsp_append + k_rsp_sample",
-                                   "achieved": round(env_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                                   "frac": round(env_gbs / PEAK_HBM_GBS, 4), "avg_us": round(env_s * 1e6, 2),
-                                   "bytes_per_env_step": RNN_ENV_BYTES}
-            out["drqn_update_us"] = round(upd_s * 1e6, 2)
-        out.update({
-            "learner": {"train_steps": c["train_steps"], "episodes": c["episodes"], "epsilon": c["epsilon"],
-                        "seq_size": c["seq_size"], **dst, "status": c["status"], "drqn_status": dst["status"]},
-            "drqn_roofline": drqn,
-        })
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            act_s = sum(act_t) / len(act_t)  # k_rnn_act's own dispatch (pm_timer_*), as rocprofv3 times it
+            env_s = sum(e[1].elapsed_time(e[2]) for e in evs) * 1e-3 / len(evs)  # overlap: env + update
+            upd_s = sum(e[2].elapsed_time(e[3]) for e in evs) * 1e-3 / len(evs)
+            fpa = RNN_FLOP_PER_ARENA // 2 if overlap else RNN_FLOP_PER_ARENA  # overlap: modelB's side only
+            achieved = n * fpa / act_s / 1e12
+            env_gbs = n * RNN_ENV_BYTES / env_s / 1e9
+            out["roofline"] = {
+                "bound": "mfma",
+                "kernel": "k_rnn_act side B: the overlapped step's act for modelB" if overlap
+                          else "k_rnn_act (both players)",
+                "timing": "the launch's own begin/end (hipExtLaunchKernel events, pm_timer_arm) "
+                          "on instrumented production steps after the timed region",
+                "compute": "v_mfma_f32_32x32x2_f32 (exact fp32; dense FP32 matrix peak 157.3 TF)",
+                "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / PEAK_FP32_TFLOPS, 4),
+                # modelB's side: 256 blocks x 256 lanes (the overlapped step's only k_rnn_act of
+                # that grid); the plain step's both-players launch has no committed pass
+                "traffic": pmc_traffic(f"k_rnn_act@{256 * 256}", "r3_rnn_pmc.json") if overlap and n == 32768 else None,
+                "avg_us": round(act_s * 1e6, 2), "flop_per_arena": fpa, "n": n}
+            if overlap:
+                out["env_update_us"] = round(env_s * 1e6, 2)  # env + sample + DRQN update, the opponents' act beside
+            else:
+                out["env_roofline"] = {"bound": "hbm", "kernel": "k_rsp_env + k_rsp_append + k_rsp_sample",
+                                       "achieved": round(env_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                       "frac": round(env_gbs / PEAK_HBM_GBS, 4), "avg_us": round(env_s * 1e6, 2),
+                                       "bytes_per_env_step": RNN_ENV_BYTES}
+                out["drqn_update_us"] = round(upd_s * 1e6, 2)
+        out["learner"] = {"train_steps": c["train_steps"], "episodes": c["episodes"], "epsilon": c["epsilon"],
+                          "seq_size": c["seq_size"], **dst, "status": c["status"], "drqn_status": dst["status"]}
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
+        if args.full:
+            out["drqn_roofline"] = drqn
+        if args.cpu_legs:
             out["cpu_baseline"] = cpu_baseline_rnn(args.cpu_seconds)
         if failed:
             out["error"] = "device status bit 0 (overwritten ring read) / shard proof failed"
@@ -678,27 +761,30 @@ def run_infer(args, dist, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         dist.all_reduce(tot)
-    # after the timed region: the megakernel's own dispatch (pm_timer_arm, as rocprofv3 times it) on
-    # `reps` launches of `chunk` steps, and the same launches bracketed by HIP events on the stream
-    reps = 3
-    ks = []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        _lib.timer_arm(_lib.PM_TIMER_ROLLOUT)
-        R.run(chunk, sync=False, replay=replay)
-    e1.record()
-    e1.synchronize()
-    ks = [_lib.timer_read(_lib.PM_TIMER_ROLLOUT) for _ in range(reps)]
-    k_s = sum(ks) / reps
-    ev_s = e0.elapsed_time(e1) * 1e-3 / reps
     st = dict(zip(STATS, tot.cpu().tolist()))
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = snapshot({"rollout_stats": tot.to(torch.float64), "env_f64": env.f64.t(), "env_i32": env.i32.t(),
+                           "obsA": env.obsA, "obsB": env.obsB, "ep_reward": R.ep_reward,
+                           **({"replay_trans": replay.trans, "replay_prios": replay.prios} if collect else {})})
+    # --full, after the timed region: the megakernel's own dispatch (pm_timer_arm, as rocprofv3 times
+    # it) on `reps` launches of `chunk` steps, and the same launches bracketed by HIP events on the stream
+    reps = 3
+    k_s = ev_s = None
+    if args.full:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            _lib.timer_arm(_lib.PM_TIMER_ROLLOUT)
+            R.run(chunk, sync=False, replay=replay)
+        e1.record()
+        e1.synchronize()
+        k_s = sum(_lib.timer_read(_lib.PM_TIMER_ROLLOUT) for _ in range(reps)) / reps
+        ev_s = e0.elapsed_time(e1) * 1e-3 / reps
     r16 = int(os.environ.get("PONGMI_ROLL16", "1") or "1")  # the library's tile choice (pm_rollout.hip roll16)
     tile16 = bool(r16 & (2 if collect else 1))
     if rank == 0:
         value = n * world * steps / dt
-        flop = n * chunk * 2 * FLOP_PER_ARENA
-        achieved = flop / k_s / 1e12
         out = {
             "metric": "env-steps/sec (whole node), QNet inference-only self-play rollout (configs[1])",
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": warm,
@@ -711,34 +797,44 @@ def run_infer(args, dist, rank, world):
                        "arenas_per_gpu": n, "global_arenas": n * world, "steps_per_launch": chunk,
                        "launches_in_timed_region": -(-steps // chunk), "parallelism": f"dp{world} (independent "
                        "arena shards, no collective)"},
-            "roofline": {"bound": "mfma", "kernel": (f"k_rollout16 (K9 on 16-arena tiles, v_mfma_f32_16x16x4_f32" if tile16
-                                                     else "k_rollout (K9 on 32-arena tiles") +
-                                                    f": both players' QNet forward + env tick, {chunk} vector steps per launch)",
-                         "compute": f"{'v_mfma_f32_16x16x4_f32' if tile16 else 'v_mfma_f32_32x32x2_f32'} (exact fp32; "
-                                    "dense FP32 matrix peak 157.3 TF)",
-                         "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_FP32_TFLOPS, 4), "traffic": infer_traffic(n, chunk, kernel="k_rollout16" if tile16 else "k_rollout"),
-                         "avg_us": round(k_s * 1e6, 1), "avg_us_per_step": round(k_s / chunk * 1e6, 4),
-                         "flop_per_env_step": 2 * FLOP_PER_ARENA, "n": n,
-                         "waves": 8 * (-(-n // 16)) if tile16 else 4 * (-(-n // 32)), "wave_slots": 256 * 4,
-                         "timing": f"pm_timer_arm dispatch of {reps} launches after the timed region; "
-                                   f"HIP events incl. the heads fold: {ev_s * 1e6:.1f} us per launch"},
             "rollout": st,
-            "stepped": time_infer_stepped(wA, pB, n) if world == 1 else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
+        if args.full:
+            flop = n * chunk * 2 * FLOP_PER_ARENA
+            achieved = flop / k_s / 1e12
+            kern = "k_rollout16" if tile16 else "k_rollout"
+            out["roofline"] = {
+                "bound": "mfma",
+                "kernel": ("k_rollout16 (K9 on 16-arena tiles, v_mfma_f32_16x16x4_f32" if tile16
+                           else "k_rollout (K9 on 32-arena tiles") +
+                          f": both players' QNet forward + env tick, {chunk} vector steps per launch)",
+                "compute": f"{'v_mfma_f32_16x16x4_f32' if tile16 else 'v_mfma_f32_32x32x2_f32'} (exact fp32; "
+                           "dense FP32 matrix peak 157.3 TF)",
+                "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / PEAK_FP32_TFLOPS, 4), "traffic": infer_traffic(n, chunk, kernel=kern),
+                "avg_us": round(k_s * 1e6, 1), "avg_us_per_step": round(k_s / chunk * 1e6, 4),
+                "flop_per_env_step": 2 * FLOP_PER_ARENA, "n": n,
+                "waves": 8 * (-(-n // 16)) if tile16 else 4 * (-(-n // 32)), "wave_slots": 256 * 4,
+                "timing": f"pm_timer_arm dispatch of {reps} launches after the timed region; "
+                          f"HIP events incl. the heads fold: {ev_s * 1e6:.1f} us per launch"}
+            out["stepped"] = time_infer_stepped(wA, pB, n) if world == 1 and not collect else None
+        if args.cpu_legs:
             # collect: the port at 4 096 arenas with the push (the 65 536-arena vector step would take
             # most of the bounded sample per step)
             out["cpu_baseline"] = cpu_baseline_infer(args.cpu_seconds, 4096 if collect else n,
                                                      replay_cap=args.memory if collect else 0)
         if collect:
-            rb = n * chunk * REPLAY_BYTES / k_s / 1e9
             out["metric"] = ("env-steps/sec (whole node), collecting self-play rollout: every transition pushed "
                              "into the PER replay ring (SURVEY 8f3)")
             out["config"]["workload"] = (f"8f3 at configs[2]'s arena count: {n} arenas/GPU, the configs[1] rollout "
                                          f"(eps 0.02 held, learner off) + memory.push of every transition into a "
                                          f"{args.memory}-row PER ring, {chunk} vector steps per launch")
             out["config"]["replay_cap"] = args.memory
+            out["replay"] = {"pos": replay.pos, "size": replay.size}
+        if collect and args.full:
+            rb = n * chunk * REPLAY_BYTES / k_s / 1e9
             out["roofline"]["kernel"] = (f"{'k_rollout16_push' if tile16 else 'k_rollout_push'} (both players' QNet "
                                          f"forward + env tick + replay push, {chunk} vector steps per launch)")
             # HBM bytes per launch from the committed counter passes (profiles/r3_collect_pmc.json,
@@ -751,8 +847,6 @@ def run_infer(args, dist, rank, world):
                                       "bytes_per_transition": REPLAY_BYTES,
                                       "note": "replay-write bytes (row 64 + priority 4 + PER leaf 4) per launch / "
                                               "k_rollout_push dispatch time; the launch is MFMA-latency bound"}
-            out["stepped"] = None
-            out["replay"] = {"pos": replay.pos, "size": replay.size}
         emit(out)
     if dist is not None:
         dist.destroy_process_group()
@@ -816,19 +910,19 @@ def run_train(args, dist, rank, world):
     c1 = _play_episodes(L, episodes, _Quiet(), 4)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
+    dumped = dqn_outputs(L, c1) if args.dump_outputs else None
     B = (L.modelB_state_dict(), _lib.PM_FOLD_TRAIN)
     wA = eval_vs_model(env_kw, (L.modelA_state_dict(), _lib.PM_FOLD_TRAIN), B, eval_eps, rng=rng)
     wP = eval_vs_pool(env_kw, B, [(sd, _lib.PM_FOLD_EVAL) for sd in pool], eval_eps, rng=rng)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
     L.check_status(c1)
-    # k_learn_multi (updates 1..U-1 of a vector step) by its own dispatch, after the try
+    # --full: k_learn_multi (updates 1..U-1 of a vector step) by its own dispatch, after the try
     um = []
-    for _ in range(5):
+    for _ in range(5 if args.full else 0):
         _lib.timer_arm(_lib.PM_TIMER_LEARN_MULTI)
         L.step()
         um.append(_lib.timer_read(_lib.PM_TIMER_LEARN_MULTI))
-    multi_s = sum(um) / len(um)
     play_s, eval_s = t1 - t0, t2 - t1
     vsteps = c1["step"] - c0["step"]
     env_steps = vsteps * n
@@ -851,13 +945,17 @@ def run_train(args, dist, rank, world):
             "updates": upd, "updates_per_s": round(upd / play_s, 1), "play_s": round(play_s, 3),
             "eval_s": round(eval_s, 3), "generation_try_s": round(play_s + eval_s, 3),
             "eval": {"vs_A": wA, "vs_pool": wP},
-            "learn_multi_us_per_update": round(multi_s / max(U - 1, 1) * 1e6, 3),
-            "learn_multi_launch_us": round(multi_s * 1e6, 1),
             "reference_python_measured": {"steps_per_s": REF_LOOP_STEPS_PER_S,
                                           "note": "train_iterative.py step body (1 env step + 1 update of 256), 1 CPU "
                                                   "thread (SURVEY 6); a 2 400-episode try is ~91 k steps"},
             "vs_reference_loop": {k: round(value / v, 1) for k, v in REF_LOOP_STEPS_PER_S.items()},
         }
+        if um:
+            multi_s = sum(um) / len(um)
+            out["learn_multi_us_per_update"] = round(multi_s / max(U - 1, 1) * 1e6, 3)
+            out["learn_multi_launch_us"] = round(multi_s * 1e6, 1)
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
         emit(out)
 
 
@@ -938,7 +1036,17 @@ def main():
     ap.add_argument("--pool", type=int, default=None, help="opponent pool size (synthetic nets; 8 dqn, 4 rnn)")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--memory", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baselines, the per-kernel and "
+                         "roofline figures (instrumented steps and separate launches after the timed region) and "
+                         "the other comparisons of the workload; a plain run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left (the learner's parameters, "
+                         "observations, actions, env state, counters, ...) as DIR/<name>.npy (float32 / float64, at "
+                         "most 64 MB in all; larger arrays as a fixed sample of rows); the same arguments give the "
+                         "same inputs on every run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--updates-per-step", type=int, default=1,
                     help="dqn: PER updates of `batch` per vector step (U; SURVEY 8d: 1 default, 64 the stress "
@@ -968,7 +1076,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # configs[0]'s scalar CPU loop runs in forked worker processes: before this process touches the GPU
-    args.cpu_config0 = cpu_config0() if world == 1 and args.workload == "dqn" and not args.no_cpu_baseline else None
+    args.cpu_legs = args.full and world == 1 and not args.no_cpu_baseline
+    args.cpu_config0 = cpu_config0() if args.cpu_legs and args.workload == "dqn" else None
     rehearse = world > 1 and rehearsal(os.environ)
     if rehearse:  # ranks share the visible devices; gloo, torch.distributed all-reduce (RCCL wants one GPU per rank)
         local = local % max(torch.cuda.device_count(), 1)
@@ -1029,10 +1138,12 @@ def main():
         ae_t.append(_lib.timer_read(_lib.PM_TIMER_ACTENV))
         learn_t.append(_lib.timer_read(_lib.PM_TIMER_LEARN))
 
-    dt, _, c1 = timed_region(one_step, args.steps, dist, 0, read_timers, L.counters)
+    def at_end():
+        c = L.counters()
+        return c, (dqn_outputs(L, c) if args.dump_outputs and rank == 0 else None)
+
+    dt, _, (c1, dumped) = timed_region(one_step, args.steps, dist, 0, read_timers, at_end, instrument=args.full)
     same = replicas_identical(dist, L.paramsB)
-    ae_s = sum(ae_t) / len(ae_t)  # the launches' own durations, as rocprofv3 --kernel-trace times them
-    learn_s = sum(learn_t) / len(learn_t)
     c = L.counters()
     shards, shards_ok = shard_proof(dist, rank, world, args.arenas, c["step"], c["status"], args.comm, L.grad)
     failed = c["status"] != 0 or not shards_ok or (dist is not None and not same)
@@ -1040,12 +1151,6 @@ def main():
     if rank == 0:
         total = args.arenas * world * args.steps
         value = total / dt
-        ahead = L.featB is not None
-        learn_flop = FLOP_PER_ARENA + (FEAT_FLOP_PER_ARENA if ahead else 0)
-        achieved = args.arenas * learn_flop / learn_s / 1e12
-        env_bytes = SP_ENV_BYTES + (FEAT_BYTES if ahead else 0)
-        env_gbs = args.arenas * env_bytes / ae_s / 1e9
-        ae_grid = (args.batch + 63) // 64 + (args.arenas + 255) // 256
         out = {
             "metric": "env-steps/sec (whole node) at 65536 arenas, 1/2/4/8 GPUs; CPU-ref baseline",
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps,
@@ -1060,33 +1165,47 @@ def main():
                        "memory_size": args.memory, "parallelism": f"dp{world} (arena shards, 1 all-reduce/update)",
                        "all_reduce": args.comm_used if world > 1 else None, "replicas_identical": same,
                        "shards": shards},
-            "roofline": {"bound": "mfma",
-                         "kernel": "k_learn launch: the double-DQN update (one workgroup) + the next step's "
-                                   "opponents' act and modelB's feature layers on the other CUs",
-                         "compute": "v_mfma_f32_32x32x2_f32 (exact fp32; dense FP32 matrix peak 157.3 TF)",
-                         "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / PEAK_FP32_TFLOPS, 4), "traffic": pmc_traffic("k_learn") if U == 1 else None,
-                         "avg_us": round(learn_s * 1e6, 2), "flop_per_arena": learn_flop, "n": args.arenas},
-            "env_roofline": {"bound": "hbm",
-                             "kernel": "k_actenv (modelB's heads + env tick + replay push + PER sample / batch "
-                                       "forward)" if ahead else "k_actenv (modelB's act + env tick + replay push + "
-                                                                "PER sample / batch forward)",
-                             "achieved": round(env_gbs, 1), "peak": PEAK_HBM_GBS,
-                             "unit": "GB/s", "frac": round(env_gbs / PEAK_HBM_GBS, 4),
-                             "traffic": pmc_traffic(f"k_actenv@{ae_grid * 256}") if U == 1 else None,
-                             "avg_us": round(ae_s * 1e6, 2), "bytes_per_env_step": env_bytes},
-            "learn_us": round(learn_s * 1e6, 2), "actenv_us": round(ae_s * 1e6, 2),
-            "learner": {"train_steps": c["train_steps"], "episodes": c["episodes"], "epsilon": c["epsilon"],
-                        "last_loss": c["last_loss"], "status": c["status"]},
         }
+        if args.full:
+            ahead = L.featB is not None
+            ae_s = sum(ae_t) / len(ae_t)  # the launches' own durations, as rocprofv3 --kernel-trace times them
+            learn_s = sum(learn_t) / len(learn_t)
+            learn_flop = FLOP_PER_ARENA + (FEAT_FLOP_PER_ARENA if ahead else 0)
+            achieved = args.arenas * learn_flop / learn_s / 1e12
+            env_bytes = SP_ENV_BYTES + (FEAT_BYTES if ahead else 0)
+            env_gbs = args.arenas * env_bytes / ae_s / 1e9
+            ae_grid = (args.batch + 63) // 64 + (args.arenas + 255) // 256
+            out.update({
+                "roofline": {"bound": "mfma",
+                             "kernel": "k_learn launch: the double-DQN update (one workgroup) + the next step's "
+                                       "opponents' act and modelB's feature layers on the other CUs",
+                             "compute": "v_mfma_f32_32x32x2_f32 (exact fp32; dense FP32 matrix peak 157.3 TF)",
+                             "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                             "frac": round(achieved / PEAK_FP32_TFLOPS, 4),
+                             "traffic": pmc_traffic("k_learn") if U == 1 else None,
+                             "avg_us": round(learn_s * 1e6, 2), "flop_per_arena": learn_flop, "n": args.arenas},
+                "env_roofline": {"bound": "hbm",
+                                 "kernel": "k_actenv (modelB's heads + env tick + replay push + PER sample / batch "
+                                           "forward)" if ahead else "k_actenv (modelB's act + env tick + replay push "
+                                                                    "+ PER sample / batch forward)",
+                                 "achieved": round(env_gbs, 1), "peak": PEAK_HBM_GBS,
+                                 "unit": "GB/s", "frac": round(env_gbs / PEAK_HBM_GBS, 4),
+                                 "traffic": pmc_traffic(f"k_actenv@{ae_grid * 256}") if U == 1 else None,
+                                 "avg_us": round(ae_s * 1e6, 2), "bytes_per_env_step": env_bytes},
+                "learn_us": round(learn_s * 1e6, 2), "actenv_us": round(ae_s * 1e6, 2),
+            })
+        out["learner"] = {"train_steps": c["train_steps"], "episodes": c["episodes"], "epsilon": c["epsilon"],
+                          "last_loss": c["last_loss"], "status": c["status"]}
         if U > 1:
             out["us_per_update"] = round(dt / args.steps / U * 1e6, 3)
             out["learn_multi"] = L.frow is not None
-        if world == 1:
+        if dumped is not None:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, dumped)}
+        if args.full and world == 1:
             out["act_full_roofline"] = time_act_full(L)
             out["env_step_roofline"] = time_env_step(args.arenas)
             out["scalar_dropin"] = time_scalar_dropin()
-            if not args.no_cpu_baseline:
+            if args.cpu_legs:
                 out["cpu_baseline"] = cpu_baseline(args.arenas, nets, args.cpu_seconds)
                 out["cpu_config0"] = args.cpu_config0
         if failed:
