@@ -3,7 +3,6 @@
 // HBM-bound: per env-step 203 algorithmic bytes (fp64 state 7x8 read + write, int32 scores /
 // bounces 12 read + write, actions 2, obs 56, rewards 8, done 1). Observations leave the kernel
 // through an LDS transpose so every store is a full 16-byte-per-lane coalesced write.
-#include <stdlib.h>
 #include <string.h>
 
 #include "pm_dev.h"
@@ -89,17 +88,16 @@ static __device__ unsigned long long pm_k1_diag[8][4096];
 // 2 reset + term rows written for done arenas only (the other rows are left as they were).
 // WT: write-through outputs (pm_dev.h st_out), chosen by the arena count at launch.
 //
-// PRO (round 5, the default): the prologue is ordered for latency. Every lane loads from a clamped
-// index (i < n ? i : n - 1), so no bounds branch splits the kernel-argument loads into two dependent
-// scalar rounds (bound n first, then the pointers: ~2 scalar-cache round trips before the first
-// vector load), and a scheduling barrier keeps every state / action load ahead of the serve draw —
-// without it the compiler interleaved ~100 Philox instructions in front of the state loads and ~200
-// in front of the score loads. Stores stay guarded by i < n. PONGMI_K1_PRO=0 selects the round-4
-// prologue (A/B). Round-5 measurements that were NOT kept (profiles/r5_k1_experiments.txt): wave-level
-// observation staging without the workgroup barrier (one store burst 4.25 us, state stores first
-// 4.19 us, against 4.11 us with the barrier), and 16-B per-lane state accesses (field pairs / quads per
-// instruction: the copy skeleton 4.12 against 3.53 us).
-template <int AR, bool INJ, bool WT, int PRO>
+// The prologue is ordered for latency (round 5). Every lane loads from a clamped index
+// (i < n ? i : n - 1), so no bounds branch splits the kernel-argument loads into two dependent scalar
+// rounds (bound n first, then the pointers: ~2 scalar-cache round trips before the first vector
+// load), and a scheduling barrier keeps every state / action load ahead of the serve draw — without
+// it the compiler interleaved ~100 Philox instructions in front of the state loads and ~200 in front
+// of the score loads. Stores stay guarded by i < n. Round-5 measurements that were NOT kept
+// (profiles/r5_k1_experiments.txt): wave-level observation staging without the workgroup barrier (one
+// store burst 4.25 us, state stores first 4.19 us, against 4.11 us with the barrier), and 16-B
+// per-lane state accesses (field pairs / quads per instruction: the copy skeleton 4.12 against 3.53 us).
+template <int AR, bool INJ, bool WT>
 __global__ __launch_bounds__(kBlock) void k_env_step(pm_env_params p, pm_env_state s, const int8_t* __restrict__ aA,
                                                      const int8_t* __restrict__ aB, float* __restrict__ obsA,
                                                      float* __restrict__ obsB, float* __restrict__ rA,
@@ -113,62 +111,60 @@ __global__ __launch_bounds__(kBlock) void k_env_step(pm_env_params p, pm_env_sta
     const int t = threadIdx.x;
     const int i = i0 + t;
     const bool full_term = tobsA && AR != 2;  // tobsA and tobsB are both set or both null
-    float oA[7] = {0}, oB[7] = {0}, tA[7], tB[7];
+    float oA[7], oB[7], tA[7], tB[7];
     int tdone = 0;
     K1_STAMP(0);
-    if ((PRO & 1) || i < n) {
-        const int il = (PRO & 1) ? (i < n ? i : n - 1) : i;  // the loads' index (clamped: no bounds branch)
-        int32_t ns = 0;
-        ServeDraw sv{};
-        if (INJ) ns = __builtin_nontemporal_load(&s.serves[il]);
-        Arena a = load_arena(s, il);
-        const int xa = aA[il], xb = aB[il];
-        if (PRO & 2) __builtin_amdgcn_sched_barrier(0);  // every load issued before the draw's first instruction
-        // the step-keyed draw depends on no load: it runs while the state is in flight, and is
-        // pinned complete ahead of the tick (the compiler would sink it into the done lanes' path)
-        if (DRAW) {
-            sv = serve_draw(p, (uint32_t)i, (uint32_t)ctr, seed, TAG_SERVE_STEP, (uint32_t)(ctr >> 32));
-            asm volatile("" ::"v"(sv.vx), "v"(sv.vy), "v"(sv.spin), "v"(sv.rad));
-        }
+    const int il = i < n ? i : n - 1;  // the loads' index (clamped: no bounds branch; n >= 1)
+    int32_t ns = 0;
+    ServeDraw sv{};
+    if (INJ) ns = __builtin_nontemporal_load(&s.serves[il]);
+    Arena a = load_arena(s, il);
+    const int xa = aA[il], xb = aB[il];
+    __builtin_amdgcn_sched_barrier(0);  // every load issued before the draw's first instruction
+    // the step-keyed draw depends on no load: it runs while the state is in flight, and is
+    // pinned complete ahead of the tick (the compiler would sink it into the done lanes' path)
+    if (DRAW) {
+        sv = serve_draw(p, (uint32_t)i, (uint32_t)ctr, seed, TAG_SERVE_STEP, (uint32_t)(ctr >> 32));
+        asm volatile("" ::"v"(sv.vx), "v"(sv.vy), "v"(sv.spin), "v"(sv.rad));
+    }
 #ifdef PM_DIAG
-        K1_DRAIN();
-        K1_STAMP(1);
+    K1_DRAIN();
+    K1_STAMP(1);
 #endif
-        float ra, rb;
-        const int d = tick(p, a, xa, xb, ra, rb);
-        K1_STAMP(2);
+    float ra, rb;
+    const int d = tick(p, a, xa, xb, ra, rb);
+    K1_STAMP(2);
+    observe(a, oA, oB);
+    if (full_term) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) { lds[2][t][k] = oA[k]; lds[3][t][k] = oB[k]; }
+    }
+    if constexpr (DRAW) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) { tA[k] = oA[k]; tB[k] = oB[k]; }
+        serve_finish(sv);  // the rare |angle| >= 135 degree redo (a branch no lane normally takes)
+        Arena r = a;
+        serve(r, sv.vx, sv.vy, sv.spin);
+        a.x = d ? r.x : a.x; a.y = d ? r.y : a.y; a.vx = d ? r.vx : a.vx; a.vy = d ? r.vy : a.vy;
+        a.spin = d ? r.spin : a.spin; a.top = d ? r.top : a.top; a.bot = d ? r.bot : a.bot;
+        a.sA = d ? 0 : a.sA; a.sB = d ? 0 : a.sB; a.bounces = d ? 0 : a.bounces;
         observe(a, oA, oB);
-        if (full_term) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) { lds[2][t][k] = oA[k]; lds[3][t][k] = oB[k]; }
+    } else if (AR && d) {  // parity mode: the injected serve of done arenas
+        if (AR == 2 && tobsA && i < n) {
+            store_row7(tobsA + (size_t)i * 7, oA);
+            store_row7(tobsB + (size_t)i * 7, oB);
         }
-        if constexpr (DRAW) {
-#pragma unroll
-            for (int k = 0; k < 7; ++k) { tA[k] = oA[k]; tB[k] = oB[k]; }
-            serve_finish(sv);  // the rare |angle| >= 135 degree redo (a branch no lane normally takes)
-            Arena r = a;
-            serve(r, sv.vx, sv.vy, sv.spin);
-            a.x = d ? r.x : a.x; a.y = d ? r.y : a.y; a.vx = d ? r.vx : a.vx; a.vy = d ? r.vy : a.vy;
-            a.spin = d ? r.spin : a.spin; a.top = d ? r.top : a.top; a.bot = d ? r.bot : a.bot;
-            a.sA = d ? 0 : a.sA; a.sB = d ? 0 : a.sB; a.bounces = d ? 0 : a.bounces;
-            observe(a, oA, oB);
-        } else if (AR && d) {  // parity mode: the injected serve of done arenas
-            if (AR == 2 && tobsA && i < n) {
-                store_row7(tobsA + (size_t)i * 7, oA);
-                store_row7(tobsB + (size_t)i * 7, oB);
-            }
-            const double* r = inject + ((size_t)il * inject_cap + (ns % inject_cap)) * 3;
-            serve(a, r[0], r[1], r[2]);
-            if (i < n) s.serves[i] = ns + 1;
-            observe(a, oA, oB);
-        }
-        if (i < n) {
-            store_arena<WT>(s, i, a);
-            st_out<WT>(&rA[i], ra);
-            st_out<WT>(&rB[i], rb);
-            done[i] = (uint8_t)d;
-            tdone = d;
-        }
+        const double* r = inject + ((size_t)il * inject_cap + (ns % inject_cap)) * 3;
+        serve(a, r[0], r[1], r[2]);
+        if (i < n) s.serves[i] = ns + 1;
+        observe(a, oA, oB);
+    }
+    if (i < n) {
+        store_arena<WT>(s, i, a);
+        st_out<WT>(&rA[i], ra);
+        st_out<WT>(&rB[i], rb);
+        done[i] = (uint8_t)d;
+        tdone = d;
     }
     K1_STAMP(3);
 #pragma unroll
@@ -254,27 +250,9 @@ __global__ __launch_bounds__(64) void k_collide1(double vn, double vt, double u,
     __hip_atomic_store(reinterpret_cast<uint32_t*>(out + 3), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Write-through K1 outputs up to kK1WtMax arenas (latency-bound sizes); PONGMI_K1_WT=0/1 forces
-// the choice (experiments).
+// Write-through K1 outputs up to kK1WtMax arenas (latency-bound sizes).
 constexpr int32_t kK1WtMax = 131072;
-int k1_write_through(int32_t n) {
-    static const int forced = [] {
-        const char* e = getenv("PONGMI_K1_WT");
-        return e && *e ? atoi(e) : -1;
-    }();
-    return forced >= 0 ? (forced != 0) : (n <= kK1WtMax);
-}
-
-// K1 prologue (PONGMI_K1_PRO, A/B; bit 0 clamped loads, bit 1 loads ahead of the draw): 3 (default)
-// both, 0 round 4's.
-int k1_prologue() {
-    static const int v = [] {
-        const char* e = getenv("PONGMI_K1_PRO");
-        const int x = e && *e ? atoi(e) : 3;
-        return x >= 0 && x <= 3 ? x : 3;
-    }();
-    return v;
-}
+bool k1_write_through(int32_t n) { return n <= kK1WtMax; }
 
 bool state_ok(const pm_env_state* s) {
     return s && s->x && s->y && s->vx && s->vy && s->spin && s->top && s->bot && s->scoreA && s->scoreB &&
@@ -310,19 +288,16 @@ extern "C" int pm_env_step(const pm_env_params* p, const pm_env_state* s, const 
     PM_REQUIRE(autoreset >= 0 && autoreset <= 2, PM_E_ARG, "pm_env_step: autoreset=%d not in {0,1,2}", autoreset);
     PM_REQUIRE(!inject || inject_cap > 0, PM_E_ARG, "pm_env_step: inject without capacity");
     PM_REQUIRE(p->speed_scale_every > 0, PM_E_ARG, "pm_env_step: speed_scale_every must be > 0");
-    using K = decltype(&k_env_step<0, false, false, 3>);
-#define PM_K1_SET(PRO)                                                                               \
-    {{{k_env_step<0, false, false, PRO>, k_env_step<0, true, false, PRO>},                           \
-      {k_env_step<1, false, false, PRO>, k_env_step<1, true, false, PRO>},                           \
-      {k_env_step<2, false, false, PRO>, k_env_step<2, true, false, PRO>}},                          \
-     {{k_env_step<0, false, true, PRO>, k_env_step<0, true, true, PRO>},                             \
-      {k_env_step<1, false, true, PRO>, k_env_step<1, true, true, PRO>},                             \
-      {k_env_step<2, false, true, PRO>, k_env_step<2, true, true, PRO>}}}
-    static const K kernels[4][2][3][2] = {PM_K1_SET(0), PM_K1_SET(1), PM_K1_SET(2), PM_K1_SET(3)};
-#undef PM_K1_SET
-    pm_launch(PM_TIMER_ENV_STEP, kernels[k1_prologue()][k1_write_through(n)][autoreset][inject != nullptr],
-              dim3(pm_blocks(n, kBlock)),
-              dim3(kBlock), pm_stream(stream), *p, *s, aA, aB, obsA, obsB, rA, rB, done, term_obsA, term_obsB, inject,
+    using K = decltype(&k_env_step<0, false, false>);
+    static const K kernels[2][3][2] = {  // [WT][AR][INJ]
+        {{k_env_step<0, false, false>, k_env_step<0, true, false>},
+         {k_env_step<1, false, false>, k_env_step<1, true, false>},
+         {k_env_step<2, false, false>, k_env_step<2, true, false>}},
+        {{k_env_step<0, false, true>, k_env_step<0, true, true>},
+         {k_env_step<1, false, true>, k_env_step<1, true, true>},
+         {k_env_step<2, false, true>, k_env_step<2, true, true>}}};
+    pm_launch(PM_TIMER_ENV_STEP, kernels[k1_write_through(n)][autoreset][inject != nullptr],
+              dim3(pm_blocks(n, kBlock)), dim3(kBlock), pm_stream(stream), *p, *s, aA, aB, obsA, obsB, rA, rB, done, term_obsA, term_obsB, inject,
               inject_cap, seed, counter, status, n);
     PM_LAUNCHED("k_env_step");
     return PM_OK;

@@ -309,9 +309,7 @@ __device__ __forceinline__ void tile_heads(const float* hf, const f32x16 (&c2)[2
 // Layer 1 (both 32-row tiles) and layer-2 tile jt of tile_hidden (pm_mfma.h), MFMA for MFMA in the same
 // order: the two layer-2 tiles are independent accumulator chains, so a wave computing one of them
 // produces exactly the registers tile_hidden gives for it.
-template <typename F>
-__device__ __forceinline__ void hidden_half(const float* lw, const float (&xs)[4], int lane, int jt, f32x16& c2,
-                                            F&& valu) {
+__device__ __forceinline__ void hidden_half(const float* lw, const float (&xs)[4], int lane, int jt, f32x16& c2) {
     const int h = lane >> 5;
     f32x16 c1[2];
     const f32x16 zero = {};
@@ -345,7 +343,6 @@ __device__ __forceinline__ void hidden_half(const float* lw, const float (&xs)[4
         c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcur.y, c1[t][4 * rq + 1], c2, 0, 0, 0);
         c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcur.z, c1[t][4 * rq + 2], c2, 0, 0, 0);
         c2 = __builtin_amdgcn_mfma_f32_32x32x2f32(wcur.w, c1[t][4 * rq + 3], c2, 0, 0, 0);
-        valu(g);  // independent VALU work, scheduled between this group's dependent MFMAs
         wcur = wnext;
         __builtin_amdgcn_sched_barrier(0);
     }

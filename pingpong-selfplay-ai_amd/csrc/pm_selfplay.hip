@@ -235,48 +235,13 @@ __device__ __forceinline__ void env_fwd_block(const pm_selfplay& sp, int f, bool
     if (mine) store_hfeat(sp.hfeat, j, nxt, lane, c2, qb, qt, rb);
 }
 
-// The fused step's sampler blocks: block b draws samples [64 b, 64 b + 64) (per_sample_block) and then
-// computes their stable rows' forward itself, one tile per wave (waves 0-1: s rows of the block's
-// samples, waves 2-3: their s' rows): no other block waits for the sample. The weight image and the
-// update's heads are staged while the sampler descends the tree.
-struct SampleFwdSmem {
-    PerSampleSmem per;
-    float lw[kLwFloats];
-    float hf[pad256(2 * 264)];  // modelB (update noise) [0, 264) | targetB (mu) [264, 528) head fragments
-    int64_t sidx[PER_BS];
-};
-__device__ __forceinline__ void sample_fwd_block(const pm_selfplay& sp, int b, SampleFwdSmem& sm) {
-    // the forward's weights are staged once the top level of the descent is done: LDS DMA in flight
-    // makes hipcc wait vmcnt(0) at the next use of a plain load, which would put the 20 KB staging in
-    // front of the chunk-sum round trip
-    sample_block(sp, b, true, sm.per, sm.sidx, [&] {
-        stage_frags_lds(sp.w_B, sm.lw, b * 5);
-        copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
-    });
-    if (!learner_active(sp)) return;  // block-uniform (sample_block returned before its first barrier)
-    __syncthreads();  // sidx, staged weights
-    PM_BLK(1);
-    const int lane = threadIdx.x & 63, B = sp.batch;
-    const int r = (int)(threadIdx.x >> 6) * 32 + (lane & 31);  // row of the block's 128: s rows, then s'
-    const bool nxt = r >= PER_BS;
-    const int js = nxt ? r - PER_BS : r;
-    const int j = b * PER_BS + js;
-    const int64_t id = sm.sidx[min(j, B - 1) - b * PER_BS];
-    const pm_ctrl* c = sp.ctrl;
-    const bool mine = j < B && !push_of(sp, c->pos, c->size, c->max_prio).covers(id);
-    f32x16 c2[2];
-    float qb[3], qt[3];
-    float rb[2];
-    batch_row_fwd(sp, sm.lw, sm.hf, sm.hf + 264, id, nxt, lane, c2, qb, qt, rb);
-    if (mine) store_hfeat(sp.hfeat, j, nxt, lane, c2, qb, qt, rb);
-}
-
-// The split variant (PONGMI_SFB=32, the default): block b draws samples [32 b, 32 b + 32) and its 4 waves
-// split the forward of the 2 tiles (s rows, s' rows) by layer-2 tile, as k_rollout16 does (pm_mfma.h
+// The fused step's sampler blocks: block b draws samples [32 b, 32 b + 32) (per_sample_block) and then
+// computes their stable rows' forward itself: no other block waits for the sample. Its 4 waves split
+// the forward of the 2 tiles (s rows, s' rows) by layer-2 tile, as k_rollout_push does (pm_mfma.h
 // hidden_half / heads_half): wave 2 k + jt computes layer-2 tile jt of tile k (24 MFMAs deep instead of
 // 40); wave jt = 0 runs the head chains over its 32 units and hands the partial sums to wave jt = 1
-// through LDS, which continues them in tile_heads' order. Every stored value is bit-identical to
-// sample_fwd_block's. s rows need only Q_B (store_hfeat stores Q_T of s' rows only).
+// through LDS, which continues them in tile_heads' order, so every stored value is bit-identical to
+// batch_row_fwd's. s rows need only Q_B (store_hfeat stores Q_T of s' rows only).
 struct SampleFwd32Smem {
     PerSampleSmem per;
     float lw[kLwFloats];
@@ -286,6 +251,9 @@ struct SampleFwd32Smem {
 };
 __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b, SampleFwd32Smem& sm) {
     constexpr int NS = PER_BS / 2;
+    // the forward's weights are staged once the top level of the descent is done: LDS DMA in flight
+    // makes hipcc wait vmcnt(0) at the next use of a plain load, which would put the 20 KB staging in
+    // front of the chunk-sum round trip
     sample_block<NS>(sp, b, true, sm.per, sm.sidx, [&] {
         stage_frags_lds(sp.w_B, sm.lw, b * 5);
         copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
@@ -306,7 +274,7 @@ __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b,
     tile_inputs(tr + (nxt ? 8 : 0), lane >> 5, xs);
     const float rb0 = tr[7], rb1 = tr[15];
     f32x16 c2;
-    hidden_half(sm.lw, xs, lane, jt, c2, [](int) {});
+    hidden_half(sm.lw, xs, lane, jt, c2);
     const float* hf0 = sm.hf;
     const float* hf1 = sm.hf + 264;
     float ab[4] = {0.f, 0.f, 0.f, 0.f}, at[4] = {0.f, 0.f, 0.f, 0.f};
@@ -552,23 +520,19 @@ __global__ __launch_bounds__(kBlock) void k_env(const pm_selfplay sp) {
     env_block<false>(sp, blk, sm, nullptr);
 }
 
-// The fused step's first kernel (pm_selfplay_actenv): blocks [0, ceil(B/64)) sample the update's batch
-// and compute its stable rows (sample_fwd_block); every other block acts for modelB and ticks its 256
+// The fused step's first kernel (pm_selfplay_actenv): blocks [0, ceil(B/32)) sample the update's batch
+// and compute its stable rows (sample_fwd_block32); every other block acts for modelB and ticks its 256
 // arenas (env_block<true>). Replaces k_act_sp(PM_ACT_B) + k_env of the overlapped step, bit for bit.
 union ActEnvShared {
     ActEnvSmem ae;
-    SampleFwdSmem sf;
     SampleFwd32Smem sf32;
 };
-// NS: samples per sampler block (64: sample_fwd_block, 32: sample_fwd_block32).
-template <int NS>
 __global__ __launch_bounds__(kBlock) void k_actenv(const pm_selfplay sp) {
     __shared__ __attribute__((aligned(16))) ActEnvShared sh;
-    const int nsb = (sp.batch + NS - 1) / NS;
+    const int nsb = (sp.batch + 31) / 32;  // sampler blocks, PER_BS / 2 samples each
     if ((int)blockIdx.x < nsb) {
         PM_BLK(0);
-        if constexpr (NS == PER_BS) sample_fwd_block(sp, (int)blockIdx.x, sh.sf);
-        else sample_fwd_block32(sp, (int)blockIdx.x, sh.sf32);
+        sample_fwd_block32(sp, (int)blockIdx.x, sh.sf32);
         PM_BLK_END();
         return;
     }
@@ -899,7 +863,7 @@ __device__ __forceinline__ void push_rows_fwd2(const pm_selfplay& sp, PushFwdSme
             tile_inputs(tr + (nxt ? 8 : 0), h, xs);
             rb0 = tr[7];
             rb1 = tr[15];
-            hidden_half(sm.lw, xs, lane, jt, c2, [](int) {});
+            hidden_half(sm.lw, xs, lane, jt, c2);
             if (mine && !nxt) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) put(j, 32 * jt + rho(q) + 4 * h, relu(c2[q]));
@@ -2538,14 +2502,14 @@ bool multi_ok(const pm_selfplay* sp) {
 
 // k_learn's side blocks (launches with the next step's side-A act): one CU each (the launch's LDS), so
 // they run in ONE round beside the learner only if they fit the CUs the learner and block 1 leave, and
-// they end together only if their work is even. PONGMI_SIDE=1 (default) sizes them from the opponent
-// draw's expected rows: each net's chunk (a multiple of 256 arenas, so the act reads the env kernel's
-// lists) is expected to hold kSideRows rows (~15 full 32-row tiles for 16 waves), and the feature
-// tiles are spread over the CUs left (>= 16 per block). At configs[2] (pool 8, ratio 0.33): 86 modelA
-// blocks (768 arenas, ~515 rows), 48 pool blocks (11 776 arenas, ~486 rows), 114 feature blocks of 18
-// tiles: 250 blocks. PONGMI_SIDE=0: the round-4 grid (4x the act kernel's chunks up to 4 096 arenas,
-// 16 feature tiles: 64 + 128 + 128 side blocks, two rounds; measured r5m: modelA blocks of ~705 rows
-// end 22 us after the learner starts, the second round's feature blocks 23.8 us, the learner ~19 us).
+// they end together only if their work is even. They are sized from the opponent draw's expected
+// rows: each net's chunk (a multiple of 256 arenas, so the act reads the env kernel's lists) is
+// expected to hold kSideRows rows (~15 full 32-row tiles for 16 waves), and the feature tiles are
+// spread over the CUs left (>= 16 per block). At configs[2] (pool 8, ratio 0.33): 86 modelA blocks
+// (768 arenas, ~515 rows), 48 pool blocks (11 776 arenas, ~486 rows), 114 feature blocks of 18 tiles:
+// 250 blocks. (Round 4's grid, 4x the act kernel's chunks and 16 feature tiles, was 64 + 128 + 128
+// side blocks in two rounds; measured r5m: modelA blocks of ~705 rows ended 22 us after the learner
+// started, the second round's feature blocks 23.8 us, the learner ~19 us.)
 struct LearnGrid {
     ActGrid g;
     int ftiles;
@@ -2561,13 +2525,6 @@ int side_sleep() {
     const char* n = getenv("PONGMI_SIDE_NAP");
     const int roles = e && *e ? atoi(e) : 2, nap = n && *n ? atoi(n) : 8;
     return (roles & 3) | (std::max(0, std::min(nap, 64)) << 8);
-}
-int side_mode() {
-    static const int v = [] {
-        const char* e = getenv("PONGMI_SIDE");
-        return e && *e ? atoi(e) : 1;
-    }();
-    return v;
 }
 int device_cus() {
     static const int v = [] {
@@ -2586,10 +2543,6 @@ int side_chunk(double p) {
 }
 LearnGrid learn_grid(const pm_selfplay* sp) {
     const int ntiles = feat_ntiles(sp->n);
-    if (side_mode() == 0)
-        return LearnGrid{ActGrid{sp->n, sp->n_pool + 1, std::min(4 * sp->chunk_A, kListMax),
-                                 std::min(4 * sp->chunk_P, kListMax), 0},
-                         kFeatTilesLearn};
     const double pp = sp->n_pool > 0 ? sp->pool_ratio : 0.0;
     const ActGrid g{sp->n, sp->n_pool + 1, side_chunk(1.0 - pp), side_chunk(sp->n_pool > 0 ? pp / sp->n_pool : 0.0), 0};
     // the feature blocks take the CUs the act blocks leave; when (nearly) none are left (n well above
@@ -2656,16 +2609,8 @@ extern "C" int pm_selfplay_env(const pm_selfplay* sp, void* stream) {
 extern "C" int pm_selfplay_actenv(const pm_selfplay* sp, void* stream) {
     int rc = check(sp);
     if (rc) return rc;
-    // PONGMI_SFB: samples per sampler block, 32 (split forward, default) or 64 (round-4 blocks)
-    static const int sfb = [] {
-        const char* e = getenv("PONGMI_SFB");
-        return e && atoi(e) == 64 ? 64 : 32;
-    }();
-    const unsigned nsb = (unsigned)((sp->batch + sfb - 1) / sfb);
-    if (sfb == 64)
-        pm_launch(PM_TIMER_ACTENV, k_actenv<64>, dim3(nsb + pm_blocks(sp->n, kBlock)), dim3(kBlock), pm_stream(stream), *sp);
-    else
-        pm_launch(PM_TIMER_ACTENV, k_actenv<32>, dim3(nsb + pm_blocks(sp->n, kBlock)), dim3(kBlock), pm_stream(stream), *sp);
+    const unsigned nsb = pm_blocks(sp->batch, 32);  // sampler blocks (sample_fwd_block32)
+    pm_launch(PM_TIMER_ACTENV, k_actenv, dim3(nsb + pm_blocks(sp->n, kBlock)), dim3(kBlock), pm_stream(stream), *sp);
     PM_LAUNCHED("k_actenv");
     return PM_OK;
 }

@@ -39,8 +39,7 @@ def main():
     nb = (n + 255) // 256
     buf = (ctypes.c_uint64 * (8 * 1024))()
     blk = (ctypes.c_uint64 * (8 * 4096))()
-    sfb = 64 if os.environ.get("PONGMI_SFB") == "64" else 32  # samples per k_actenv sampler block
-    nsb = (256 + sfb - 1) // sfb
+    nsb = (256 + 31) // 32  # k_actenv's sampler blocks: 32 samples each
     acc, samp, staged = [], [], []
     for _ in range(20):
         if L.overlap:  # the production step's launches, read right after the fused act + env kernel

@@ -8,8 +8,8 @@
 # tasks:
 #   suite      the whole `-m gpu` suite + smoke()
 #   env        tests/test_gpu_env.py only (K1 parity)
-#   k1         K1 A/B: parity of the A/B variant, graph-timed floor probe (tools/k1_floor), product K1 with
-#              PONGMI_K1_PRO=1 / 0 (tools/k1_time.py, bench.time_env_step), rocprofv3 kernel traces
+#   k1         K1: parity (tests/test_gpu_env.py), graph-timed floor probe (tools/k1_floor), product K1 timed
+#              twice (tools/k1_time.py, bench.time_env_step), one rocprofv3 kernel trace
 #   k1stamp    per-wave K1 phase cycles (diag build, tools/k1_stamps.py)
 #   stampsnw   tools/stamps.py on the PM_DIAG_NOWAIT diag build (libpongmi_diag_nw.so)
 #   stamps     diag build: k_learn phase stamps of the overlapped step (tools/stamps.py) and k_actenv's
@@ -25,7 +25,7 @@
 #   pmcrnn     the same for the RNN bench (tools/pmc_rnn_passes.sh)
 #   pmcinfer   the same for the configs[1] inference rollout (2 000-step launches)
 #   drqn       tests/test_gpu_drqn.py + tools/drqn_time.py
-#   side       k_learn's side blocks (act / feature) per role, under PONGMI_SIDE 1 / 0 (diag build)
+#   side       k_learn's side blocks (act / feature) per role (diag build)
 #   roll       k_rollout16 per-step phase cycles (tools/roll_stamps.py, diag build)
 #   ab:VAR=v1,v2  tests/test_gpu_selfplay.py under each value, then the default bench interleaved twice
 #   drqnab:VAR=v1,v2  tests/test_gpu_drqn.py under v1, then tools/drqn_time.py interleaved three times
@@ -53,25 +53,17 @@ run_task() {
     env)
       timeout -k 10 300 $PYT tests/test_gpu_env.py > $OUT/${tag}_env.log 2>&1 && tail -1 $OUT/${tag}_env.log ;;
     k1)
-      for pro in ${K1_PARITY_PROS:-0}; do
-        PONGMI_K1_PRO=$pro timeout -k 10 300 $PYT tests/test_gpu_env.py > $OUT/${tag}_env_pro$pro.log 2>&1 &&
-            tail -1 $OUT/${tag}_env_pro$pro.log || return 1
-      done &&
+      timeout -k 10 300 $PYT tests/test_gpu_env.py > $OUT/${tag}_env.log 2>&1 && tail -1 $OUT/${tag}_env.log &&
       timeout -k 10 120 ./tools/k1_floor 65536 > $OUT/${tag}_k1_floor.jsonl 2>&1 && cat $OUT/${tag}_k1_floor.jsonl &&
-      for pro in ${K1_PROS:-3 0 3 0}; do
-        echo "== PONGMI_K1_PRO=$pro" >> $OUT/${tag}_k1_time.txt
-        PONGMI_K1_PRO=$pro timeout -k 10 120 python3 tools/k1_time.py 65536 262144 >> $OUT/${tag}_k1_time.txt 2>&1 || return 1
+      for rep in 1 2; do
+        timeout -k 10 120 python3 tools/k1_time.py 65536 262144 >> $OUT/${tag}_k1_time.txt 2>&1 || return 1
       done && grep -v amdgpu.ids $OUT/${tag}_k1_time.txt &&
-      for pro in ${K1_PROF_PROS:-3 0}; do
-        PONGMI_K1_PRO=$pro timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv \
-            -d $OUT/${tag}_prof_k1_pro$pro -o k -- python3 tools/k1_time.py 65536 \
-            > $OUT/${tag}_prof_k1_pro$pro.log 2>&1 || return 1
-      done && echo K1_OK ;;
+      timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv \
+          -d $OUT/${tag}_prof_k1 -o k -- python3 tools/k1_time.py 65536 \
+          > $OUT/${tag}_prof_k1.log 2>&1 && echo K1_OK ;;
     k1stamp)
-      for pro in ${K1_PROF_PROS:-3 0}; do
-        PONGMI_K1_PRO=$pro timeout -k 10 120 python3 tools/k1_stamps.py > $OUT/${tag}_k1_stamps_pro$pro.txt 2>&1 &&
-            grep -v amdgpu.ids $OUT/${tag}_k1_stamps_pro$pro.txt || return 1
-      done ;;
+      timeout -k 10 120 python3 tools/k1_stamps.py > $OUT/${tag}_k1_stamps.txt 2>&1 &&
+          grep -v amdgpu.ids $OUT/${tag}_k1_stamps.txt ;;
     stamps)
       timeout -k 10 180 python3 tools/stamps.py > $OUT/${tag}_stamps.txt 2>&1 && grep -v amdgpu.ids $OUT/${tag}_stamps.txt &&
       timeout -k 10 180 python3 tools/env_blocks.py > $OUT/${tag}_env_blocks.txt 2>&1 && grep -v amdgpu.ids $OUT/${tag}_env_blocks.txt ;;
@@ -122,11 +114,9 @@ run_task() {
               echo "$var=$v rep$rep $(python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(round(d['value']/1e9,4), d['ms_per_step'])" $OUT/${tag}_ab_${var}_${v//\//_}_$rep.json)" || return 1
         done
       done ;;
-    side)  # k_learn's side-block timeline (diag build), under each PONGMI_SIDE grid
-      for v in ${SIDE_MODES:-1 0}; do
-        PONGMI_SIDE=$v timeout -k 10 180 python3 tools/side_blocks.py > $OUT/${tag}_side_$v.txt 2>&1 &&
-            echo "PONGMI_SIDE=$v" && grep -v amdgpu.ids $OUT/${tag}_side_$v.txt || return 1
-      done ;;
+    side)  # k_learn's side-block timeline (diag build)
+      timeout -k 10 180 python3 tools/side_blocks.py > $OUT/${tag}_side.txt 2>&1 &&
+          grep -v amdgpu.ids $OUT/${tag}_side.txt ;;
     drqnab:*)  # drqnab:VAR=v1,v2 — tests/test_gpu_drqn.py under v1, then tools/drqn_time.py interleaved three times
       spec=${1#drqnab:}; var=${spec%%=*}; vals=${spec#*=}; first=${vals%%,*}
       env $var=$first timeout -k 10 300 $PYT tests/test_gpu_drqn.py > $OUT/${tag}_drqnab.log 2>&1 &&

@@ -5,8 +5,7 @@ diagnostic library's s_memtime stamps (libpongmi_diag.so; never the product libr
 
 Phases (lane 0 of every wave): 0 start | 1 every load landed (a vmcnt(0) drain: diag only) |
 2 draw + tick done | 3 reset select + state/reward stores issued | 4 LDS staging + barrier |
-5 observation rows + term rows issued | 6 every store drained. PONGMI_K1_PRO=0 selects round 4's
-prologue (A/B)."""
+5 observation rows + term rows issued | 6 every store drained."""
 import ctypes
 import os
 import sys

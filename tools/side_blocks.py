@@ -35,19 +35,16 @@ def main():
     for _ in range(40):
         L.step()
     torch.cuda.synchronize()
-    # the host's learn_grid (pm_selfplay.hip), PONGMI_SIDE 1 (default) / 0, on a 256-CU device
+    # the host's learn_grid (pm_selfplay.hip) on a 256-CU device
     ntiles = (n + 31) // 32
-    if os.environ.get("PONGMI_SIDE") == "0":
-        c0, c1, ft = min(4 * L.sp.chunk_A, 4096), min(4 * L.sp.chunk_P, 4096), 16
-    else:
-        def chunk(p):
-            return 16384 if p <= 0 else min(16384, max(256, -(-480 / p // 256) * 256))
-        c0, c1 = int(chunk(1 - L.sp.pool_ratio)), int(chunk(L.sp.pool_ratio / 8))
+
+    def chunk(p):
+        return 16384 if p <= 0 else min(16384, max(256, -(-480 / p // 256) * 256))
+    c0, c1 = int(chunk(1 - L.sp.pool_ratio)), int(chunk(L.sp.pool_ratio / 8))
     na0, na1 = (n + c0 - 1) // c0, (n + c1 - 1) // c1
     nact = na0 + 8 * na1
-    if os.environ.get("PONGMI_SIDE") != "0":
-        left = 256 - 2 - nact
-        ft = min(max(-(-ntiles // left), 16), ntiles)
+    left = 256 - 2 - nact
+    ft = min(max(-(-ntiles // left), 16), ntiles)
     nfeat = (ntiles + ft - 1) // ft
     side = (ctypes.c_uint64 * (4 * 1024))()
     buf = (ctypes.c_uint64 * 256)()
