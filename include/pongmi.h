@@ -23,13 +23,14 @@
 #ifndef PONGMI_H
 #define PONGMI_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 23
+#define PM_ABI_VERSION 24
 
 #define PM_OK 0
 #define PM_E_ARG (-1)     /* null / inconsistent argument */
@@ -191,6 +192,21 @@ int pm_play(const pm_env_params* p, const float* w_nets, int32_t n_nets, const i
             const int32_t* blk_range, int32_t n_blocks, const int32_t* order, const double* serves, int32_t n,
             int32_t max_steps, int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
             void* stream);
+
+/* K8 for QNetRNN players (csrc/pm_playrnn.hip): pm_play's whole-episode launch for pairs in which at
+ * least one side is a QNetRNN (tests/test_round_robin.py:290-330, tests/arena.py:294-320 and the
+ * evaluators of scripts/train_rnn_iterative.py). Slots, ranges, serves, outputs and *status are
+ * pm_play's. Player ids in blk_nets: >= 0 QNet w_qnet[id] (PM_QNET_NW floats each), -1
+ * HardcodedBallFollower, <= -2 QNetRNN w_rnn[-2 - id] (PM_RNN_NW floats each, pm_rnn_fold); both
+ * weight arrays 16-B aligned. A block whose pair has no QNetRNN side, or an id out of range, plays
+ * nothing and adds to *status. Every episode starts from a zero (h, c) (init_hidden); the states
+ * live in hc_scratch (device, 16-B aligned, pm_play_rnn_scratch_bytes(n_blocks) bytes, contents
+ * irrelevant on entry). max_steps bounds the ticks of each block over all its slots. */
+int pm_play_rnn(const pm_env_params* p, const float* w_qnet, int32_t n_qnet, const float* w_rnn, int32_t n_rnn,
+                const int32_t* blk_nets, const int32_t* blk_range, int32_t n_blocks, const int32_t* order,
+                const double* serves, int32_t n, int32_t max_steps, float* hc_scratch,
+                int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status, void* stream);
+size_t pm_play_rnn_scratch_bytes(int32_t n_blocks);
 
 /* K9 — inference-only self-play rollout, `steps` vector steps in one launch (BASELINE configs[1];
  * csrc/pm_rollout.hip). Replaces the act/step loop of scripts/train_iterative.py:239-242 with the

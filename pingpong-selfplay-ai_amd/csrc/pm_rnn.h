@@ -172,29 +172,21 @@ __device__ __forceinline__ void add_bias_lds(const float* b, f32x16& acc) {
     }
 }
 
-// One acting step of QNetRNN for group g of a block's arena list (tiles 4g .. 4g+3, one per wave):
-// q values out through `out`, (h, c) rows updated in HBM. Block-wide (all 4 waves, barriers).
-// (h, c) are read from hin / cin (null: hst / cst, in place) and written to hst / cst.
-template <typename Out>
-__device__ __forceinline__ void rnn_group(const float* __restrict__ w, float* ring, const float* hw,
-                                          const float* __restrict__ obs, float* hst, float* cst,
-                                          const uint8_t* __restrict__ reset, const int* list, int count, int g,
-                                          const Out& out, const float* hin = nullptr, const float* cin = nullptr) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-    const int row = (4 * g + wave) * 32 + (lane & 31);
-    const bool valid = row < count;
-    const int arena = list[min(row, count - 1)];
-    float* hs = hst + (size_t)arena * 128;
-    float* cs = cst + (size_t)arena * 128;
-    const float* hr = (hin ? hin : hst) + (size_t)arena * 128;
-    const float* cr = (cin ? cin : cst) + (size_t)arena * 128;
-    const bool zero = reset != nullptr && reset[arena] != 0;
+// The block-wide QNetRNN step behind rnn_group: one 32-column tile per wave, the layer-1 inputs xs
+// (tile_inputs order) already in registers. (h, c) of this lane's column are read from hr / cr
+// (zero: taken as 0, the rows are not read) and, if valid, written to hs / cs; the column's q values
+// (the same in both lane halves) go to fin(q). All 4 waves run it together (one barrier per ring
+// stage), so every wave must call it the same number of times. g: the caller's group (diagnostic
+// stamps only).
+template <typename Fin>
+__device__ __forceinline__ void rnn_core(const float* __restrict__ w, float* ring, const float* hw,
+                                         const float (&xs)[4], bool zero, bool valid, const float* hr,
+                                         const float* cr, float* hs, float* cs, int g, const Fin& fin) {
+    const int lane = threadIdx.x & 63, h = lane >> 5;
     PM_STG(0);
     PM_STG_CLK(40);
     stage_issue(w, 0, ring);  // F2 first half lands while the prologue runs
-    // ---- prologue: inputs, layer 1, biases, h_prev into the B-operand registers
-    float xs[4];
-    tile_inputs(obs + (size_t)arena * 7, h, xs);
+    // ---- prologue: layer 1, biases, h_prev into the B-operand registers
     float xb[8][16];  // gate K-steps t = 0..7: B operands (features 0..3, h_prev 4..7)
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -321,9 +313,32 @@ __device__ __forceinline__ void rnn_group(const float* __restrict__ w, float* ri
     a2 += hw[515];
     const float mean = ((a0 + a1) + a2) / 3.0f;
     const float q[3] = {v + (a0 - mean), v + (a1 - mean), v + (a2 - mean)};
-    out(arena, valid && h == 0, q);
+    fin(q);
     PM_STG(46);
     PM_STG_CLK(47);
+}
+
+// One acting step of QNetRNN for group g of a block's arena list (tiles 4g .. 4g+3, one per wave):
+// q values out through `out`, (h, c) rows updated in HBM. Block-wide (all 4 waves, barriers).
+// (h, c) are read from hin / cin (null: hst / cst, in place) and written to hst / cst.
+template <typename Out>
+__device__ __forceinline__ void rnn_group(const float* __restrict__ w, float* ring, const float* hw,
+                                          const float* __restrict__ obs, float* hst, float* cst,
+                                          const uint8_t* __restrict__ reset, const int* list, int count, int g,
+                                          const Out& out, const float* hin = nullptr, const float* cin = nullptr) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+    const int row = (4 * g + wave) * 32 + (lane & 31);
+    const bool valid = row < count;
+    const int arena = list[min(row, count - 1)];
+    float* hs = hst + (size_t)arena * 128;
+    float* cs = cst + (size_t)arena * 128;
+    const float* hr = (hin ? hin : hst) + (size_t)arena * 128;
+    const float* cr = (cin ? cin : cst) + (size_t)arena * 128;
+    const bool zero = reset != nullptr && reset[arena] != 0;
+    float xs[4];
+    tile_inputs(obs + (size_t)arena * 7, h, xs);
+    rnn_core(w, ring, hw, xs, zero, valid, hr, cr, hs, cs, g,
+             [&](const float (&q)[3]) { out(arena, valid && h == 0, q); });
 }
 
 // ---------------------------------------------------------------- the split tile (side A's tail)

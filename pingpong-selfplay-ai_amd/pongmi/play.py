@@ -7,6 +7,9 @@ arenas by pair (first-appearance order, arenas ascending within a pair), splits 
 block ranges, and hands the serves over in slot order. Net id FOLLOWER (-1) is the
 HardcodedBallFollower. Used by pongmi.evaluate (eval_vs_model / eval_vs_pool) and
 pongmi.tournament (QNet / ball-follower pairs).
+
+play_rnn is the same for pairs with a QNetRNN player (pm_play_rnn, csrc/pm_playrnn.hip): the
+block's RNN sides take one block-wide K5 step per tick, their (h, c) per column in a device scratch.
 """
 import ctypes
 
@@ -18,15 +21,18 @@ from ._lib import PM_QNET_NW, check, ptr, stream_ptr
 from .env import env_params
 
 FOLLOWER = -1
+RNN_BASE = -2        # play_rnn: QNetRNN net k has id RNN_BASE - k
 COLUMNS = 128        # arenas a block plays at once
 MAX_SLOTS = 1024     # slots per block range (the kernel stages them in LDS)
 TARGET_BLOCKS = 512  # 2 blocks (8 waves) per CU on 256 CUs before ranges grow past one slot per column
+TARGET_BLOCKS_RNN = 256  # play_rnn: one block per CU (its LDS ring and register file fill the CU)
 
 
 def plan_blocks(netA, netB, per_block=None):
     """(blk_nets int32 [nb, 2], blk_range int32 [nb, 2] = (start, count), order int32 [E]: arena of
-    each slot) for per-arena net ids. per_block: slots per block (default: COLUMNS, or more once the
-    arenas would need more than TARGET_BLOCKS blocks, so columns refill instead of adding waves)."""
+    each slot) for per-arena net ids (any integers: play_rnn's QNetRNN ids lie below FOLLOWER).
+    per_block: slots per block (default: COLUMNS, or more once the arenas would need more than
+    TARGET_BLOCKS blocks, so columns refill instead of adding waves)."""
     netA = np.asarray(netA, np.int64).reshape(-1)
     netB = np.asarray(netB, np.int64).reshape(-1)
     if netA.shape != netB.shape:
@@ -38,7 +44,8 @@ def plan_blocks(netA, netB, per_block=None):
         raise ValueError(f"per_block must be in [1, {MAX_SLOTS}]")
     if E == 0:
         return np.zeros((0, 2), np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
-    ka, kb = netA + 1, netB + 1
+    shift = max(1, -int(min(netA.min(), netB.min())))  # ids start at FOLLOWER, or at the lowest QNetRNN id
+    ka, kb = netA + shift, netB + shift
     width = int(kb.max()) + 1
     key = ka * width + kb
     span = int(key.max()) + 1
@@ -109,5 +116,64 @@ def play(env_kw, w_nets, netA, netB, serves, device="cuda", max_steps=1_000_000,
     st = int(status.item())
     if st or (out[2] < 0).any():
         raise RuntimeError(f"pm_play: {int((out[2] < 0).sum())} arenas did not finish within {max_steps} steps "
+                           f"({st} invalid ids or cut episodes)")
+    return out
+
+
+def rnn_id(k):
+    """play_rnn's player id of QNetRNN net k (and back: rnn_id(rnn_id(k)) == k)."""
+    return RNN_BASE - k
+
+
+def play_rnn(env_kw, w_qnet, w_rnn, idA, idB, serves, device="cuda", max_steps=1_000_000, per_block=None):
+    """Play one greedy episode per arena, at least one QNetRNN on each pair. w_qnet: effective QNet
+    weights [nets, PM_QNET_NW] or None; w_rnn: effective QNetRNN weights [nets, PM_RNN_NW]
+    (pongmi.rnn.fold); idA / idB: per-arena player ids (>= 0 QNet, FOLLOWER, rnn_id(k) QNetRNN k);
+    serves [E, 3] (vx, vy, spin). Every episode starts from a zero hidden state. Returns host arrays
+    (scoreA int32 [E], scoreB int32 [E], length int32 [E], last int8 [E]) as play does."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    serves = np.ascontiguousarray(np.asarray(serves, np.float64).reshape(-1, 3))
+    E = serves.shape[0]
+    sA = torch.zeros(E, dtype=torch.int32, device=dev)
+    sB = torch.zeros(E, dtype=torch.int32, device=dev)
+    length = torch.full((E,), -1, dtype=torch.int32, device=dev)
+    last = torch.zeros(E, dtype=torch.int8, device=dev)
+    if E == 0:
+        return sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy()
+    if per_block is None:
+        per_block = min(MAX_SLOTS, COLUMNS * max(1, -(-E // (COLUMNS * TARGET_BLOCKS_RNN))))
+    blk_nets, blk_range, order = plan_blocks(idA, idB, per_block)
+    if (blk_nets.min(1) > RNN_BASE).any():
+        raise ValueError("play_rnn: every pair needs a QNetRNN player (use play for the others)")
+
+    def weights(w, width):
+        if w is None:
+            return torch.zeros((1, width), dtype=torch.float32, device=dev), 0
+        w = w.to(dev, torch.float32).reshape(-1, width).contiguous()
+        return w, int(w.shape[0])
+    wq, n_qnet = weights(w_qnet, PM_QNET_NW)
+    wr, n_rnn = weights(w_rnn, _lib.PM_RNN_NW)
+    if int(blk_nets.max()) >= n_qnet:
+        raise ValueError(f"QNet id {int(blk_nets.max())} but only {n_qnet} QNets given")
+    if RNN_BASE - int(blk_nets.min()) >= n_rnn:
+        raise ValueError(f"QNetRNN id {RNN_BASE - int(blk_nets.min())} but only {n_rnn} QNetRNNs given")
+    host = np.concatenate([blk_nets.reshape(-1), blk_range.reshape(-1), order]).astype(np.int32)
+    d_int = torch.from_numpy(host).to(dev)  # one copy: nets | ranges | order
+    nb = blk_nets.shape[0]
+    d_serves = torch.from_numpy(np.ascontiguousarray(serves[order])).to(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib.pm_play_rnn_scratch_bytes(nb)) // 4, dtype=torch.float32, device=dev)
+    prm = env_params(**env_kw)
+    # the kernel bounds a block's ticks over all its slots: max_steps per episode x slots per column
+    per_col = -(-int(blk_range[:, 1].max()) // COLUMNS)
+    block_steps = min(int(max_steps) * per_col + per_col, 2**31 - 1)
+    check(lib.pm_play_rnn(ctypes.byref(prm), ptr(wq), n_qnet, ptr(wr), n_rnn, ptr(d_int), ptr(d_int[2 * nb:]), nb,
+                          ptr(d_int[4 * nb:]), ptr(d_serves), E, block_steps, ptr(scratch), ptr(sA), ptr(sB),
+                          ptr(length), ptr(last), ptr(status), stream_ptr()), "pm_play_rnn")
+    out = (sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy())
+    st = int(status.item())
+    if st or (out[2] < 0).any():
+        raise RuntimeError(f"pm_play_rnn: {int((out[2] < 0).sum())} arenas did not finish within {max_steps} steps "
                            f"({st} invalid ids or cut episodes)")
     return out

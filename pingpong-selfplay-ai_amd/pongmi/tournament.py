@@ -9,10 +9,13 @@ the serve the reference's would, and all episodes run at once:
 
   * episodes between QNet / ball-follower players run start to finish in the match megakernel
     (K8, pongmi.play: both nets staged per block, arenas in registers, one launch);
-  * in episodes with a QNetRNN player, QNet participants act through pm_qnet_q on their arenas
-    (eval mode: NoisyLinear mu, as load_model_universal leaves them, :181-185);
-  * QNetRNN participants through pm_rnn_q with (h, c) per arena and side, from zero state;
-  * HardcodedBallFollower through the same comparison as :207-228 (float32, numpy 2 semantics).
+  * episodes with a QNetRNN player run in the same kind of launch (pm_play_rnn, pongmi.play_rnn:
+    the RNN sides take one block-wide K5 step per tick, (h, c) per column from zero state);
+  * the stepped path (rnn="stepped") plays those episodes tick by tick instead: QNet participants act
+    through pm_qnet_q on their arenas (eval mode: NoisyLinear mu, as load_model_universal leaves
+    them, :181-185), QNetRNN participants through pm_rnn_q with (h, c) per arena and side, from zero
+    state, HardcodedBallFollower through the same comparison as :207-228 (float32, numpy 2
+    semantics). Both paths give the same episodes.
 
 load_model_universal keeps the reference's checkpoint key order, its legacy fc.* -> dueling mapping
 (:144-168) and strictness, and loads with torch.load(weights_only=True). The returned frames have
@@ -116,13 +119,16 @@ class _Player:
         out.index_copy_(0, rows, a.to(out.dtype))
 
 
-def play_matches(env_params, models, plan, device="cuda", rng=None, max_steps=1_000_000):
+def play_matches(env_params, models, plan, device="cuda", rng=None, max_steps=1_000_000, rnn="fused"):
     """Play every episode of `plan` at once. models: name -> (module or "HardcodedAgent", type);
     plan: [(name_A, name_B, episodes)] in the order the reference plays them (its serves are drawn
     from `rng` / the global random stream in that order, one env.reset() per episode).
     Episodes between QNet / ball-follower players run in the match megakernel (K8, pongmi.play);
-    episodes with a QNetRNN player step all their arenas in lockstep (K5 + K1 per tick).
+    episodes with a QNetRNN player in its QNetRNN form (pm_play_rnn) or, with rnn="stepped", all their
+    arenas in lockstep (K5 + K1 per tick); both give the same episodes.
     Returns [(name_A, name_B, score_A, score_B)] per episode, in plan order."""
+    if rnn not in ("fused", "stepped"):
+        raise ValueError(f"rnn must be 'fused' or 'stepped', not {rnn!r}")
     rng = _pyrandom if rng is None else rng
     env_kw = {k: v for k, v in dict(env_params).items() if k not in ("render_size", "enable_render")}
     cfg = env_config(**env_kw)
@@ -132,14 +138,15 @@ def play_matches(env_params, models, plan, device="cuda", rng=None, max_steps=1_
         return []
     serves = np.array([draw_serve(rng, cfg) for _ in range(n)], np.float64).reshape(n, 3)
     score = np.zeros((n, 2), np.int64)
-    rnn = {nm for nm, (_, typ) in models.items() if typ == "QNetRNN"}
-    stepped = np.array([a in rnn or b in rnn for a, b in eps], bool)
+    recurrent = {nm for nm, (_, typ) in models.items() if typ == "QNetRNN"}
+    stepped = np.array([a in recurrent or b in recurrent for a, b in eps], bool)
     if (~stepped).any():
         score[~stepped] = _play_fused(env_kw, models, [eps[k] for k in np.nonzero(~stepped)[0]], serves[~stepped],
                                       device, max_steps)
     if stepped.any():
-        score[stepped] = _play_stepped(env_kw, models, [eps[k] for k in np.nonzero(stepped)[0]], serves[stepped],
-                                       device, max_steps)
+        play_recurrent = _play_fused_rnn if rnn == "fused" else _play_stepped
+        score[stepped] = play_recurrent(env_kw, models, [eps[k] for k in np.nonzero(stepped)[0]], serves[stepped],
+                                        device, max_steps)
     return [(a, b, int(score[k, 0]), int(score[k, 1])) for k, (a, b) in enumerate(eps)]
 
 
@@ -156,6 +163,25 @@ def _play_fused(env_kw, models, eps, serves, device, max_steps):
             weights.append(_qnet.fold(module.packed().to(device), _lib.PM_FOLD_EVAL)[0])
     w = torch.stack(weights) if weights else None
     sA, sB, _, _ = play(env_kw, w, [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps)
+    return np.stack([sA, sB], 1)
+
+
+def _play_fused_rnn(env_kw, models, eps, serves, device, max_steps):
+    """Episodes with a QNetRNN player in the match megakernel's QNetRNN form: [E, 2] final scores."""
+    from .play import FOLLOWER, play_rnn, rnn_id
+    ids, wq, wr = {}, [], []
+    for nm in dict.fromkeys([x for ab in eps for x in ab]):
+        module, typ = models[nm]
+        if typ == HARDCODED:
+            ids[nm] = FOLLOWER
+        elif typ == "QNetRNN":  # eval mode: NoisyLinear mu
+            ids[nm] = rnn_id(len(wr))
+            wr.append(_rnn.fold(module.packed().to(device), _lib.PM_FOLD_EVAL)[0])
+        else:
+            ids[nm] = len(wq)
+            wq.append(_qnet.fold(module.packed().to(device), _lib.PM_FOLD_EVAL)[0])
+    sA, sB, _, _ = play_rnn(env_kw, torch.stack(wq) if wq else None, torch.stack(wr) if wr else None,
+                            [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps)
     return np.stack([sA, sB], 1)
 
 
