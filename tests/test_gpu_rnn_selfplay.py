@@ -13,6 +13,12 @@
    update runs exactly when len(memory) > batch * min_episodes_for_training_start, epsilon decays
    once per finished episode;
 3. determinism, and two data-parallel ranks (gradient sum + contributing-rank count) stay identical.
+
+The `_ragged` tests repeat 1, 2 and the overlapped / split-tile identities at arena counts that are
+no multiple of the 256-arena env block (1, 255, 257, 300: a partial last block, its partial opponent
+list, staging rows past n, the episode append's scan over a short block), with an empty pool (every
+opponent id stays 0) and a pool of 64 (65 nets: no opponent lists, the act compacts); the opponent
+id never exceeds the pool in any case.
 """
 import numpy as np
 import pytest
@@ -85,22 +91,14 @@ def _check_rnn_act(who, a_dev, q_dev, h_dev, c_dev, q_or, h_or, c_or, eps, seed,
     return int(inb.sum()), int(explore.sum()), err
 
 
-@pytest.mark.parametrize("n,max_steps,nsteps,eps", [(256, 1000, 60, 0.0), (256, 24, 60, 0.3), (32768, 1000, 40, 0.0),
-                                                    (32768, 1000, 40, 0.3)])
-def test_rnn_selfplay_steps_match_oracle(golden, orc, n, max_steps, nsteps, eps):
-    """max_steps = 24 exercises the max_episode_steps cut (:751): the episode ends (new opponent,
-    serve, zero (h, c), counters) but the trajectory goes on until a done. n = 32 768 is configs[4]'s
-    full arena count; eps = 0.3 exercises modelB's epsilon branch (which still advances (h, c),
-    :375-380) on ~30 % of the arenas, with epsilon decaying per finished episode."""
+def _selfplay_steps_vs_oracle(L, pool_sds, nsteps, orc):
+    """`nsteps` plain vector steps of learner L (overlap=False, record_q=True, no training; modelA =
+    _rnn_sd(7), the pool = pool_sds) checked step by step against the oracle: both players' acts, the
+    env tick, the ring record, the bookkeeping, the next opponent and serve, the counters."""
     from pongmi.rnn import unpack_state_dict
-    # overlap=False: this test reads the opponents' (h, c) after every step, which the overlapped
-    # step has already advanced for the next one (test_rnn_overlapped_step_is_bitwise_identical)
-    pool_sds = [_rnn_sd(200 + k) for k in range(2)]
-    from pongmi.rnn_selfplay import RNNSelfPlayLearner
-    L = RNNSelfPlayLearner(ENV_KW, n, _golden_sd(golden("rnn")), _rnn_sd(7), pool_sds, epsilon=eps,
-                           min_epsilon=0.0, pool_ratio=0.5, min_episodes_for_training_start=10 ** 6, memory_size=4096,
-                           seed=3, max_episode_steps=max_steps, overlap=False, record_q=True)
     n, sp = L.n, L.sp
+    eps, max_steps = L.counters()["epsilon"], sp.max_steps
+    assert L.n_pool == len(pool_sds) and not L.overlap
     # the opponents act in eval mode (mu only): modelA, then the pool nets (:609-621)
     effA = [orc.rnn_effective({k: v.numpy() for k, v in sd.items()}, False) for sd in [_rnn_sd(7)] + pool_sds]
     arenas = np.arange(n)
@@ -165,8 +163,9 @@ def test_rnn_selfplay_steps_match_oracle(golden, orc, n, max_steps, nsteps, eps)
         ln = pre["el"] + 1
         ns = pre["i32"][3]
         q = orc.philox(np.arange(n), orc.TAG_OPP, ns, 0, sp.seed_env)
-        use_pool = orc.u53(q[0], q[1]) < sp.pool_ratio
-        newopp = np.where(use_pool, 1 + orc.below(q[2], L.n_pool), 0)
+        use_pool = (orc.u53(q[0], q[1]) < sp.pool_ratio) & (L.n_pool > 0)  # `pool and random() < ratio` (:735)
+        newopp = np.where(use_pool, 1 + orc.below(q[2], max(L.n_pool, 1)), 0)
+        assert post["opp"].min() >= 0 and post["opp"].max() <= L.n_pool, f"step {k}: opponent id past the pool"
         vx, vy, spn = orc.philox_serve(pv, np.arange(n), ns, sp.seed_env)
         assert np.array_equal(post["opp"][e], newopp[e]) and np.array_equal(post["opp"][~e], pre["opp"][~e])
         assert np.all(post["er"][e] == 0) and np.array_equal(post["er"][~e], er[~e])
@@ -188,24 +187,70 @@ def test_rnn_selfplay_steps_match_oracle(golden, orc, n, max_steps, nsteps, eps)
         finished += int(d.sum())
         cut += int((e & ~d).sum())
         long_traj = max(long_traj, int(ln[d].max()) if d.any() else 0)
-    print(f"\nrnn act vs oracle, n={n} eps={eps}: {2 * n * nsteps} decisions, {in_band} greedy ones in the "
+    print(f"\nrnn act vs oracle, n={n} pool={L.n_pool} max_steps={max_steps} eps={eps}: {finished} episodes finished, "
+          f"{cut} cut; {2 * n * nsteps} decisions, {in_band} greedy ones in the "
           f"tie band (either near-max accepted; {worst['mismatch_in_band']} of them differ from the oracle's argmax), "
           f"{explored} epsilon-branch ones exact; max error / tolerance q {worst['q']:.3f} h {worst['h']:.3f} "
           f"c {worst['c']:.3f}; max abs error q {worst['dq']:.2e} h {worst['dh']:.2e} c {worst['dc']:.2e}")
     assert in_band <= 2 * n * nsteps // 100  # the band is rare (< 1 % of decisions)
     if eps > 0:
         assert explored > 0.2 * eps * n * nsteps
-    assert finished > (50 if max_steps == 1000 else 10)  # episodes did end and restart during the run
+    # episodes did end and restart during the run: the n = 256 thresholds (50 / 10 finished, 100 cut),
+    # per arena (a fifth to a third of the counts in test_rnn_selfplay_steps_match_oracle's docstring)
+    assert finished > (50 if max_steps == 1000 else 10) * n / 256
     if max_steps < 1000:
-        assert cut > 100 and long_traj > max_steps  # cuts happened; a stored trajectory spanned a cut
+        assert cut > 100 * n / 256 and long_traj > max_steps  # cuts happened; a stored trajectory spanned a cut
     else:
         assert cut == 0
+    if L.n_pool == 0:
+        assert not L.opp.any()
     assert L.counters()["train_steps"] == 0
 
 
-def test_rnn_sequence_buffer_and_training(golden):
-    T, B, cap = 8, 64, 3000
-    L = _learner(golden, n=2048, n_pool=2, epsilon=1.0, min_epsilon=0.05, epsilon_decay=0.999, memory_size=cap,
+def _oracle_learner(golden, n, n_pool, max_steps, eps):
+    # overlap=False: these tests read the opponents' (h, c) after every step, which the overlapped
+    # step has already advanced for the next one (test_rnn_overlapped_step_is_bitwise_identical)
+    from pongmi.rnn_selfplay import RNNSelfPlayLearner
+    pool_sds = [_rnn_sd(200 + k) for k in range(n_pool)]
+    L = RNNSelfPlayLearner(ENV_KW, n, _golden_sd(golden("rnn")), _rnn_sd(7), pool_sds, epsilon=eps,
+                           min_epsilon=0.0, pool_ratio=0.5, min_episodes_for_training_start=10 ** 6, memory_size=4096,
+                           seed=3, max_episode_steps=max_steps, overlap=False, record_q=True)
+    return L, pool_sds
+
+
+@pytest.mark.parametrize("n,max_steps,nsteps,eps", [(256, 1000, 60, 0.0), (256, 24, 60, 0.3), (32768, 1000, 40, 0.0),
+                                                    (32768, 1000, 40, 0.3)])
+def test_rnn_selfplay_steps_match_oracle(golden, orc, n, max_steps, nsteps, eps):
+    """max_steps = 24 exercises the max_episode_steps cut (:751): the episode ends (new opponent,
+    serve, zero (h, c), counters) but the trajectory goes on until a done. n = 32 768 is configs[4]'s
+    full arena count; eps = 0.3 exercises modelB's epsilon branch (which still advances (h, c),
+    :375-380) on ~30 % of the arenas, with epsilon decaying per finished episode. Finished / cut
+    episodes the float64 oracle loop (oracle acting, the same Philox draws) gives for these cases:
+    259 / 0, 266 / 277, 20280 / 0, 21802 / 0."""
+    L, pool_sds = _oracle_learner(golden, n, 2, max_steps, eps)
+    _selfplay_steps_vs_oracle(L, pool_sds, nsteps, orc)
+
+
+@pytest.mark.parametrize("n,n_pool,max_steps,nsteps,eps", [(1, 2, 1000, 120, 0.3), (255, 2, 1000, 60, 0.3),
+                                                           (257, 2, 24, 60, 0.3), (300, 0, 1000, 60, 0.0),
+                                                           (300, 64, 1000, 40, 0.3)])
+def test_rnn_selfplay_steps_match_oracle_ragged(golden, orc, n, n_pool, max_steps, nsteps, eps):
+    """The same step-by-step check at sizes that are no multiple of the 256-arena env block (the ABI
+    takes any 0 < n <= 262 144): one arena; 255 / 257 / 300 arenas — a partial last env block, its
+    partial opponent list, staging rows past n, the episode append's scan over a short block; an
+    empty pool (every opponent id stays 0); a pool of 64 (65 nets: no opponent lists, the act
+    compacts). Finished / cut episodes the float64 oracle loop gives for these cases: 2 / 0, 288 / 0,
+    267 / 278, 330 / 0, 215 / 0."""
+    L, pool_sds = _oracle_learner(golden, n, n_pool, max_steps, eps)
+    _selfplay_steps_vs_oracle(L, pool_sds, nsteps, orc)
+
+
+def _sequence_buffer_and_training(golden, n, cap, every):
+    """140 random-play steps with training on: the update runs exactly when the reference's condition
+    holds, the buffer wraps, every `every`-th stored episode is one contiguous trajectory of >= T
+    steps ending in done, the sampled batch is made of windows of stored episodes."""
+    T, B = 8, 64
+    L = _learner(golden, n=n, n_pool=2, epsilon=1.0, min_epsilon=0.05, epsilon_decay=0.999, memory_size=cap,
                  min_episodes_for_training_start=1, seed=11)
     trained = 0
     for k in range(140):
@@ -228,8 +273,8 @@ def test_rnn_sequence_buffer_and_training(golden):
     eps_tab = L.episodes().numpy()
     assert len(eps_tab) == cap
     now = c["step"]
-    for arena, start, length in eps_tab[::7]:
-        assert length >= T and start + length - 1 <= now - 1 and now - 1 - start < L.depth
+    for arena, start, length in eps_tab[::every]:
+        assert 0 <= arena < n and length >= T and start + length - 1 <= now - 1 and now - 1 - start < L.depth
         rec = ring[(start + np.arange(length)) % L.depth, arena]
         bits = rec[:, 15].view(np.int32)
         assert np.all(bits[:-1] >> 8 == 0) and bits[-1] >> 8 == 1
@@ -238,6 +283,25 @@ def test_rnn_sequence_buffer_and_training(golden):
     obs, nxt = L.learner.obs.cpu().numpy(), L.learner.next.cpu().numpy()
     done = L.learner.done.cpu().numpy()
     assert np.array_equal(obs[:, 1:], nxt[:, :-1]) and np.all(done[:, :-1] == 0)
+    return L, ring, eps_tab
+
+
+def test_rnn_sequence_buffer_and_training(golden):
+    _sequence_buffer_and_training(golden, n=2048, cap=3000, every=7)
+
+
+def test_rnn_sequence_buffer_and_training_ragged(golden):
+    """n = 300 (a partial last env block: its staging rows and the append's scan over a short block),
+    a buffer of 400 episodes (the oracle loop stores ~1000 in 140 steps: it wraps), every stored
+    episode checked; each sampled sequence is found as a window of one stored episode in the ring."""
+    L, ring, eps_tab = _sequence_buffer_and_training(golden, n=300, cap=400, every=1)
+    obs = L.learner.obs.cpu().numpy()
+    windows = set()
+    for arena, start, length in eps_tab:
+        rec = ring[(start + np.arange(length)) % L.depth, arena, 0:7]
+        for s0 in range(length - L.T + 1):
+            windows.add(rec[s0:s0 + L.T].tobytes())
+    assert all(o.tobytes() in windows for o in obs)
 
 
 def test_rnn_selfplay_deterministic(golden):
@@ -333,13 +397,9 @@ def test_rnn_updates_per_step(golden):
     assert enabled > 10 and A.learner.stats()["steps"] == U * enabled
 
 
-@pytest.mark.parametrize("U", [1, 2])
-def test_rnn_overlapped_step_is_bitwise_identical(golden, U):
-    """pm_rnn_selfplay_step_overlap (the next step's opponent act on a side stream beside the DRQN
-    update, modelB's act only in the step) against the plain step: every state, action, ring record,
-    parameter and counter equal, also across a pool model added and a modelA swap mid-run."""
+def _overlapped_step_is_bitwise_identical(golden, n, U):
     from pongmi import _lib
-    kw = dict(n=1024, n_pool=2, epsilon=0.3, memory_size=2000, min_episodes_for_training_start=1, seed=6,
+    kw = dict(n=n, n_pool=2, epsilon=0.3, memory_size=2000, min_episodes_for_training_start=1, seed=6,
               updates_per_step=U)
     A = _learner(golden, overlap=False, **kw)
     B = _learner(golden, overlap=True, **kw)
@@ -371,17 +431,26 @@ def test_rnn_overlapped_step_is_bitwise_identical(golden, U):
     assert A.learner.stats()["steps"] == B.learner.stats()["steps"] > 0
 
 
-@pytest.mark.parametrize("split_r", ["0", "3"])
-def test_rnn_split_tiles_are_bitwise_identical(golden, monkeypatch, split_r):
-    """The overlapped step's side-A act with its groups from `split_r` on run as split tiles
-    (rnn_tile_split: one 32-arena tile per block, the ring's four pieces on the four waves; forced
-    with PONGMI_RNN_SPLIT_R, "0" = every group) equals the same step with splitting off
-    (PONGMI_RNN_SPLIT=0): opponents' actions, q-driven decisions, (h, c), ring records, modelB."""
-    kw = dict(n=1024, n_pool=3, epsilon=0.3, memory_size=2000, min_episodes_for_training_start=1, seed=8)
+@pytest.mark.parametrize("U", [1, 2])
+def test_rnn_overlapped_step_is_bitwise_identical(golden, U):
+    """pm_rnn_selfplay_step_overlap (the next step's opponent act on a side stream beside the DRQN
+    update, modelB's act only in the step) against the plain step: every state, action, ring record,
+    parameter and counter equal, also across a pool model added and a modelA swap mid-run."""
+    _overlapped_step_is_bitwise_identical(golden, 1024, U)
+
+
+def test_rnn_overlapped_step_is_bitwise_identical_ragged(golden):
+    """The same at n = 300 (a partial last env block and opponent list, ragged last groups on both
+    sides of the act), U = 1; the oracle loop stores its 65th episode at step ~18, so training runs."""
+    _overlapped_step_is_bitwise_identical(golden, 300, 1)
+
+
+def _split_tiles_are_bitwise_identical(golden, monkeypatch, n, split_r, nsteps, swap_at):
+    kw = dict(n=n, n_pool=3, epsilon=0.3, memory_size=2000, min_episodes_for_training_start=1, seed=8)
     A = _learner(golden, overlap=True, **kw)
     B = _learner(golden, overlap=True, **kw)
-    for k in range(30):
-        if k == 20:
+    for k in range(nsteps):
+        if k == swap_at:
             for L in (A, B):
                 L.set_modelA(_rnn_sd(302))
         monkeypatch.setenv("PONGMI_RNN_SPLIT", "0")
@@ -394,6 +463,21 @@ def test_rnn_split_tiles_are_bitwise_identical(golden, monkeypatch, split_r):
     assert torch.equal(A.hA, B.hA) and torch.equal(A.cA, B.cA) and torch.equal(A.aA, B.aA)
     assert torch.equal(A.learner.params, B.learner.params) and torch.equal(A.trans, B.trans)
     assert A.counters() == B.counters() and A.learner.stats()["steps"] > 0
+
+
+@pytest.mark.parametrize("split_r", ["0", "3"])
+def test_rnn_split_tiles_are_bitwise_identical(golden, monkeypatch, split_r):
+    """The overlapped step's side-A act with its groups from `split_r` on run as split tiles
+    (rnn_tile_split: one 32-arena tile per block, the ring's four pieces on the four waves; forced
+    with PONGMI_RNN_SPLIT_R, "0" = every group) equals the same step with splitting off
+    (PONGMI_RNN_SPLIT=0): opponents' actions, q-driven decisions, (h, c), ring records, modelB."""
+    _split_tiles_are_bitwise_identical(golden, monkeypatch, 1024, split_r, 30, 20)
+
+
+def test_rnn_split_tiles_are_bitwise_identical_ragged(golden, monkeypatch):
+    """The same at n = 300 with every group split (PONGMI_RNN_SPLIT_R=0): each net's last group is
+    partial, so split tiles with fewer than 32 rows and groups without a fourth tile both occur."""
+    _split_tiles_are_bitwise_identical(golden, monkeypatch, 300, "0", 40, 30)
 
 
 @pytest.mark.parametrize("change", [None, "modelA"])
