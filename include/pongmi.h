@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 24
+#define PM_ABI_VERSION 25
 
 #define PM_OK 0
 #define PM_E_ARG (-1)     /* null / inconsistent argument */
@@ -207,6 +207,32 @@ int pm_play_rnn(const pm_env_params* p, const float* w_qnet, int32_t n_qnet, con
                 const double* serves, int32_t n, int32_t max_steps, float* hc_scratch,
                 int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status, void* stream);
 size_t pm_play_rnn_scratch_bytes(int32_t n_blocks);
+
+/* K8 with tick records: pm_play / pm_play_rnn (same arguments, same results) that also store every
+ * tick of chosen arenas, so a match can be watched or checked tick by tick after the launch.
+ * rec_row[i] (device, [n]) is arena i's record row in [0, n_rec), or -1 for an arena that is not
+ * recorded (an entry outside [-1, n_rec) records nothing and adds to *status; two arenas must not
+ * share a row). Row r holds rec_cap ticks; tick t (0 = the first step after the serve) of row r is
+ *   rec_f64[r][t][7]    x, y, vx, vy, spin, top paddle x, bottom paddle x after the tick
+ *                       (pm_env_state's field order),
+ *   rec_q[r][t][2][3]   the q values player A's and player B's argmax consumed on this tick
+ *                       (quiet NaNs for a HardcodedBallFollower side),
+ *   rec_i32[r][t][5]    action A, action B, scoreA, scoreB and the bounce count after the tick.
+ * Ticks at or beyond rec_cap are not stored (length[] still reports the full length), and entries
+ * past an episode's length keep the caller's contents. The buffers are device memory of n_rec *
+ * rec_cap ticks each. n_rec < 0, or rec_cap <= 0 with n_rec > 0, is PM_E_SIZE; a null record buffer
+ * with n_rec > 0 is PM_E_ARG; n_rec == 0 launches the plain kernel. */
+int pm_play_rec(const pm_env_params* p, const float* w_nets, int32_t n_nets, const int32_t* blk_nets,
+                const int32_t* blk_range, int32_t n_blocks, const int32_t* order, const double* serves, int32_t n,
+                int32_t max_steps, int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
+                const int32_t* rec_row, int32_t n_rec, int32_t rec_cap, double* rec_f64, float* rec_q,
+                int32_t* rec_i32, void* stream);
+int pm_play_rnn_rec(const pm_env_params* p, const float* w_qnet, int32_t n_qnet, const float* w_rnn, int32_t n_rnn,
+                    const int32_t* blk_nets, const int32_t* blk_range, int32_t n_blocks, const int32_t* order,
+                    const double* serves, int32_t n, int32_t max_steps, float* hc_scratch,
+                    int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
+                    const int32_t* rec_row, int32_t n_rec, int32_t rec_cap, double* rec_f64, float* rec_q,
+                    int32_t* rec_i32, void* stream);
 
 /* K9 — inference-only self-play rollout, `steps` vector steps in one launch (BASELINE configs[1];
  * csrc/pm_rollout.hip). Replaces the act/step loop of scripts/train_iterative.py:239-242 with the

@@ -35,6 +35,18 @@ __device__ __forceinline__ int follower(const float (&o)[7]) {  // obs: ball_x [
     return o[0] < o[4] - tol ? 0 : (o[0] > o[4] + tol ? 2 : 1);
 }
 
+// the greedy action and the q values its argmax consumed (the same in both lane halves)
+__device__ __forceinline__ int greedy(const float* lw, const float (&o)[7], int lane, float (&q)[3]) {
+    float xs[4];
+    inputs_of(o, lane >> 5, xs);
+    f32x16 c2[2];
+    tile_hidden(lw, xs, lane, c2);
+    tile_heads(lw + F_H, c2, lane, q);
+    return argmax3(q);
+}
+
+// The plain kernels' greedy: the same body, not a call of the one above. Written as a wrapper it
+// compiled k_play<false> to a different schedule than before recording existed.
 __device__ __forceinline__ int greedy(const float* lw, const float (&o)[7], int lane) {
     float xs[4];
     inputs_of(o, lane >> 5, xs);
@@ -43,6 +55,57 @@ __device__ __forceinline__ int greedy(const float* lw, const float (&o)[7], int 
     float q[3];
     tile_heads(lw + F_H, c2, lane, q);
     return argmax3(q);
+}
+
+// ---------------------------------------------------------------- tick records (the REC kernels)
+// Recorded arenas get a row of rec_cap ticks in three caller buffers; rec_row[arena] is the row, -1
+// for the arenas that are not recorded. Tick t of row r (t = the episode's tick index, from 0):
+//   f64[r][t][7]    x, y, vx, vy, spin, top paddle x, bottom paddle x after the tick
+//   q[r][t][2][3]   the q values side A's / side B's argmax consumed (quiet NaN: ball follower)
+//   i32[r][t][5]    aA, aB, scoreA, scoreB, bounce count after the tick
+// Ticks at or beyond cap are not stored. All stores come from lanes < 32 (one per column).
+struct PlayRec {
+    const int32_t* row;  // [n]
+    int32_t n_rec, cap;
+    double* f64;
+    float* q;
+    int32_t* i32;
+};
+
+// The kernels take the PlayRec as a trailing parameter pack: one PlayRec when REC, none otherwise, so
+// the REC = false kernels keep the kernel-argument segment (and with it the code) they had before
+// recording existed. rec_arg(rec...) is the PlayRec inside an `if constexpr (REC)`.
+__device__ __forceinline__ const PlayRec& rec_arg(const PlayRec& rec) { return rec; }
+
+// the record row of a column's new episode (arena already validated): one load per episode start.
+// A row outside [-1, n_rec) records nothing and adds to `bad` (counted into *status at the end).
+__device__ __forceinline__ int rec_row_of(const PlayRec& rec, int arena, int& bad) {
+    const int r = rec.row[arena];
+    if (r < -1 || r >= rec.n_rec) { bad += 1; return -1; }
+    return r;
+}
+
+__device__ __forceinline__ bool rec_here(const PlayRec& rec, int row, int t, int lane) {
+    return row >= 0 && t < rec.cap && lane < 32;
+}
+
+__device__ __forceinline__ void rec_q(const PlayRec& rec, int row, int t, int side, const float (&q)[3]) {
+    float* d = rec.q + ((size_t)row * rec.cap + t) * 6 + side * 3;
+    d[0] = q[0]; d[1] = q[1]; d[2] = q[2];
+}
+
+__device__ __forceinline__ void rec_q_none(const PlayRec& rec, int row, int t, int side) {
+    const float nan = __builtin_nanf("");
+    const float q[3] = {nan, nan, nan};
+    rec_q(rec, row, t, side, q);
+}
+
+__device__ __forceinline__ void rec_tick(const PlayRec& rec, int row, int t, const Arena& a, int aA, int aB) {
+    const size_t k = (size_t)row * rec.cap + t;
+    double* f = rec.f64 + k * 7;
+    f[0] = a.x; f[1] = a.y; f[2] = a.vx; f[3] = a.vy; f[4] = a.spin; f[5] = a.top; f[6] = a.bot;
+    int32_t* i = rec.i32 + k * 5;
+    i[0] = aA; i[1] = aB; i[2] = a.sA; i[3] = a.sB; i[4] = a.bounces;
 }
 
 }  // namespace pm

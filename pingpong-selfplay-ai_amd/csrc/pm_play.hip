@@ -41,6 +41,11 @@ struct PlayShared {
 // Column c of a wave (both lane halves) plays slots of its block's range one after another: slot
 // c first, then the next unclaimed slot (LDS counter) whenever its episode ends. The slot table
 // (arena + serve per slot) is staged in LDS with the weights, so a refill is an LDS read.
+//
+// REC = true is the recording instantiation (pm_play_rec): a column reads its arena's record row when
+// it starts a slot and, after each tick, lanes < 32 of a recorded column store the tick (pm_play.h
+// PlayRec). REC = false is pm_play's kernel, with no `rec` argument at all.
+template <bool REC, typename... Rec>
 __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, const float* __restrict__ w, int n_nets,
                                                      const int32_t* __restrict__ blk_nets,
                                                      const int32_t* __restrict__ blk_range,
@@ -48,7 +53,8 @@ __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, cons
                                                      const double* __restrict__ serves, int n, int max_steps,
                                                      int32_t* __restrict__ scoreA, int32_t* __restrict__ scoreB,
                                                      int32_t* __restrict__ length, int8_t* __restrict__ last,
-                                                     int32_t* __restrict__ status) {
+                                                     int32_t* __restrict__ status, const Rec... rec) {
+    static_assert(sizeof...(Rec) == (REC ? 1 : 0), "one PlayRec when recording, none otherwise");
     __shared__ __attribute__((aligned(16))) PlayShared sm;
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, col = lane & 31;
@@ -69,6 +75,7 @@ __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, cons
     const int s0 = wv * 32 + col;  // this column's first slot
     int slot = s0 < live ? s0 : -1;
     int arena = -1, bad = 0, len = 0;
+    int row = -1;  // REC: the running episode's record row
     Arena a;
     serve(a, 0.0, 0.0, 0.0);
     bool done = true;
@@ -81,6 +88,7 @@ __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, cons
             len = 0;
             done = false;
             if (arena < 0 || arena >= n) { bad += 1; done = true; arena = -1; }
+            if constexpr (REC) row = done ? -1 : rec_row_of(rec_arg(rec...), arena, bad);
             slot = -2;  // claim another when this episode ends
         }
         if (__ballot(done && slot == -2) != 0) {  // wave-uniform
@@ -93,11 +101,35 @@ __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, cons
         if (__ballot(!done) == 0 || t >= max_steps) break;  // wave-uniform
         float oA[7], oB[7];
         observe(a, oA, oB);
-        const int aA = netA >= 0 ? greedy(sm.lw[0], oA, lane) : follower(oA);
-        const int aB = netB >= 0 ? greedy(sm.lw[1], oB, lane) : follower(oB);
+        int aA, aB;
+        if constexpr (REC) {
+            const PlayRec& r = rec_arg(rec...);
+            const bool here = !done && rec_here(r, row, len, lane);  // tick index len: before ++len
+            float q[3];
+            if (netA >= 0) {
+                aA = greedy(sm.lw[0], oA, lane, q);
+                if (here) rec_q(r, row, len, 0, q);
+            } else {
+                aA = follower(oA);
+                if (here) rec_q_none(r, row, len, 0);
+            }
+            if (netB >= 0) {
+                aB = greedy(sm.lw[1], oB, lane, q);
+                if (here) rec_q(r, row, len, 1, q);
+            } else {
+                aB = follower(oB);
+                if (here) rec_q_none(r, row, len, 1);
+            }
+        } else {
+            aA = netA >= 0 ? greedy(sm.lw[0], oA, lane) : follower(oA);
+            aB = netB >= 0 ? greedy(sm.lw[1], oB, lane) : follower(oB);
+        }
         if (!done) {
             float rA, rB;
             const int d = tick(p, a, aA, aB, rA, rB);
+            if constexpr (REC) {
+                if (rec_here(rec_arg(rec...), row, len, lane)) rec_tick(rec_arg(rec...), row, len, a, aA, aB);
+            }
             ++len;
             if (d) {
                 if (lane < 32) {
@@ -118,22 +150,52 @@ __global__ __launch_bounds__(kPlayBlock) void k_play(const pm_env_params p, cons
     }
 }
 
+// the checks and the launch behind pm_play (rec == nullptr) and pm_play_rec
+int play_launch(const char* who, const pm_env_params* p, const float* w_nets, int32_t n_nets, const int32_t* blk_nets,
+                const int32_t* blk_range, int32_t n_blocks, const int32_t* order, const double* serves, int32_t n,
+                int32_t max_steps, int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
+                const PlayRec* rec, void* stream) {
+    PM_REQUIRE(n >= 0 && n_blocks >= 0 && n_nets >= 0 && max_steps >= 0, PM_E_SIZE,
+               "%s: n=%d n_blocks=%d n_nets=%d max_steps=%d", who, n, n_blocks, n_nets, max_steps);
+    if (rec) {
+        PM_REQUIRE(rec->n_rec >= 0 && (rec->n_rec == 0 || rec->cap > 0), PM_E_SIZE, "%s: n_rec=%d rec_cap=%d", who,
+                   rec->n_rec, rec->cap);
+        PM_REQUIRE(rec->n_rec == 0 || (rec->row && rec->f64 && rec->q && rec->i32), PM_E_ARG,
+                   "%s: null record buffer", who);
+    }
+    if (n_blocks == 0) return PM_OK;
+    PM_REQUIRE(p && blk_nets && blk_range && order && serves && scoreA && scoreB && length && last && status,
+               PM_E_ARG, "%s: null buffer", who);
+    PM_REQUIRE(n_nets == 0 || (w_nets && (((uintptr_t)w_nets) & 15) == 0), PM_E_ARG,
+               "%s: w_nets must be non-null and 16-byte aligned", who);
+    PM_REQUIRE(p->speed_scale_every > 0, PM_E_ARG, "%s: speed_scale_every must be > 0", who);
+    if (rec && rec->n_rec > 0)
+        hipLaunchKernelGGL((k_play<true, PlayRec>), dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p, w_nets,
+                           n_nets, blk_nets, blk_range, order, serves, n, max_steps, scoreA, scoreB, length, last,
+                           status, *rec);
+    else
+        hipLaunchKernelGGL(k_play<false>, dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p, w_nets, n_nets,
+                           blk_nets, blk_range, order, serves, n, max_steps, scoreA, scoreB, length, last, status);
+    PM_LAUNCHED("k_play");
+    return PM_OK;
+}
+
 }  // namespace
 
 extern "C" int pm_play(const pm_env_params* p, const float* w_nets, int32_t n_nets, const int32_t* blk_nets,
                        const int32_t* blk_range, int32_t n_blocks, const int32_t* order, const double* serves,
                        int32_t n, int32_t max_steps, int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last,
                        int32_t* status, void* stream) {
-    PM_REQUIRE(n >= 0 && n_blocks >= 0 && n_nets >= 0 && max_steps >= 0, PM_E_SIZE,
-               "pm_play: n=%d n_blocks=%d n_nets=%d max_steps=%d", n, n_blocks, n_nets, max_steps);
-    if (n_blocks == 0) return PM_OK;
-    PM_REQUIRE(p && blk_nets && blk_range && order && serves && scoreA && scoreB && length && last && status,
-               PM_E_ARG, "pm_play: null buffer");
-    PM_REQUIRE(n_nets == 0 || (w_nets && (((uintptr_t)w_nets) & 15) == 0), PM_E_ARG,
-               "pm_play: w_nets must be non-null and 16-byte aligned");
-    PM_REQUIRE(p->speed_scale_every > 0, PM_E_ARG, "pm_play: speed_scale_every must be > 0");
-    hipLaunchKernelGGL(k_play, dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p, w_nets, n_nets, blk_nets,
-                       blk_range, order, serves, n, max_steps, scoreA, scoreB, length, last, status);
-    PM_LAUNCHED("k_play");
-    return PM_OK;
+    return play_launch("pm_play", p, w_nets, n_nets, blk_nets, blk_range, n_blocks, order, serves, n, max_steps,
+                       scoreA, scoreB, length, last, status, nullptr, stream);
+}
+
+extern "C" int pm_play_rec(const pm_env_params* p, const float* w_nets, int32_t n_nets, const int32_t* blk_nets,
+                           const int32_t* blk_range, int32_t n_blocks, const int32_t* order, const double* serves,
+                           int32_t n, int32_t max_steps, int32_t* scoreA, int32_t* scoreB, int32_t* length,
+                           int8_t* last, int32_t* status, const int32_t* rec_row, int32_t n_rec, int32_t rec_cap,
+                           double* rec_f64, float* rec_q, int32_t* rec_i32, void* stream) {
+    const PlayRec rec{rec_row, n_rec, rec_cap, rec_f64, rec_q, rec_i32};
+    return play_launch("pm_play_rec", p, w_nets, n_nets, blk_nets, blk_range, n_blocks, order, serves, n, max_steps,
+                       scoreA, scoreB, length, last, status, &rec, stream);
 }

@@ -57,11 +57,45 @@ __device__ __forceinline__ int side_action(int kind, const float* __restrict__ w
     return kind == KIND_QNET ? greedy(sm.lw, o, lane) : follower(o);
 }
 
+// side_action for the recording kernel: a lane with `here` set also stores the q values the argmax
+// consumed as tick t of its record row, at once (they are not kept across the other side's step: the
+// kernel has no register to spare).
+__device__ __forceinline__ int side_action_rec(int kind, const float* __restrict__ w_rnn, PlayRnnShared& sm, int side,
+                                               const float (&o)[7], bool zero, bool valid, float* hc, int lane,
+                                               const PlayRec& rec, bool here, int row, int t) {
+    if (kind == KIND_RNN) {  // block-uniform
+        float xs[4];
+        inputs_of(o, lane >> 5, xs);
+        int a = 1;
+        rnn_core(w_rnn, sm.ring, sm.hw[side], xs, zero, valid, hc, hc + 128, hc, hc + 128, 0,
+                 [&](const float (&q)[3]) {
+                     a = argmax3(q);
+                     if (here) rec_q(rec, row, t, side, q);
+                 });
+        return a;
+    }
+    if (kind == KIND_QNET) {
+        float q[3];
+        const int a = greedy(sm.lw, o, lane, q);
+        if (here) rec_q(rec, row, t, side, q);
+        return a;
+    }
+    if (here) rec_q_none(rec, row, t, side);
+    return follower(o);
+}
+
+// REC = true is the recording instantiation (pm_play_rnn_rec), as k_play's: the record row is read
+// when a column starts a slot, and lanes < 32 of a recorded column store each tick (pm_play.h
+// PlayRec). No barrier is added and the loop stays block-uniform. REC = false is pm_play_rnn's
+// kernel, with no `rec` argument at all.
+template <bool REC, typename... Rec>
 __global__ __launch_bounds__(kPlayBlock, 1) void k_play_rnn(
     const pm_env_params p, const float* __restrict__ w_qnet, int n_qnet, const float* __restrict__ w_rnn, int n_rnn,
     const int32_t* __restrict__ blk_nets, const int32_t* __restrict__ blk_range, const int32_t* __restrict__ order,
     const double* __restrict__ serves, int n, int max_steps, float* hc_scratch, int32_t* __restrict__ scoreA,
-    int32_t* __restrict__ scoreB, int32_t* __restrict__ length, int8_t* __restrict__ last, int32_t* __restrict__ status) {
+    int32_t* __restrict__ scoreB, int32_t* __restrict__ length, int8_t* __restrict__ last, int32_t* __restrict__ status,
+    const Rec... rec) {
+    static_assert(sizeof...(Rec) == (REC ? 1 : 0), "one PlayRec when recording, none otherwise");
     __shared__ __attribute__((aligned(16))) PlayRnnShared sm;
     const int b = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, col = lane & 31;
@@ -94,6 +128,7 @@ __global__ __launch_bounds__(kPlayBlock, 1) void k_play_rnn(
     const int s0 = wv * 32 + col;  // this column's first slot
     int slot = s0 < live ? s0 : -1;
     int arena = -1, bad = 0, len = 0;
+    int row = -1;  // REC: the running episode's record row
     Arena a;
     serve(a, 0.0, 0.0, 0.0);
     bool done = true, fresh = false;
@@ -114,18 +149,30 @@ __global__ __launch_bounds__(kPlayBlock, 1) void k_play_rnn(
             done = false;
             fresh = true;
             if (arena < 0 || arena >= n) { bad += 1; done = true; arena = -1; }
+            if constexpr (REC) row = done ? -1 : rec_row_of(rec_arg(rec...), arena, bad);
             slot = -2;  // claim another when this episode ends
         }
         // block-uniform exit: nothing live and nobody left to claim a slot, or the tick budget
         if (!__syncthreads_or(!done || slot == -2) || t >= max_steps) break;
         float oA[7], oB[7];
         observe(a, oA, oB);
-        const int aA = side_action(kA, wA, sm, 0, oA, fresh, !done, hcA, lane);
-        const int aB = side_action(kB, wB, sm, 1, oB, fresh, !done, hcB, lane);
+        int aA, aB;
+        if constexpr (REC) {
+            const PlayRec& r = rec_arg(rec...);
+            const bool here = !done && rec_here(r, row, len, lane);  // tick index len: before ++len
+            aA = side_action_rec(kA, wA, sm, 0, oA, fresh, !done, hcA, lane, r, here, row, len);
+            aB = side_action_rec(kB, wB, sm, 1, oB, fresh, !done, hcB, lane, r, here, row, len);
+        } else {
+            aA = side_action(kA, wA, sm, 0, oA, fresh, !done, hcA, lane);
+            aB = side_action(kB, wB, sm, 1, oB, fresh, !done, hcB, lane);
+        }
         fresh = false;
         if (!done) {
             float rA, rB;
             const int d = tick(p, a, aA, aB, rA, rB);
+            if constexpr (REC) {
+                if (rec_here(rec_arg(rec...), row, len, lane)) rec_tick(rec_arg(rec...), row, len, a, aA, aB);
+            }
             ++len;
             if (d) {
                 if (lane < 32) {
@@ -155,25 +202,61 @@ extern "C" size_t pm_play_rnn_scratch_bytes(int32_t n_blocks) {
     return n_blocks > 0 ? (size_t)n_blocks * 2 * kPlayArenas * kHcFloats * sizeof(float) : 0;
 }
 
+namespace {
+
+// the checks and the launch behind pm_play_rnn (rec == nullptr) and pm_play_rnn_rec
+int play_rnn_launch(const char* who, const pm_env_params* p, const float* w_qnet, int32_t n_qnet, const float* w_rnn,
+                    int32_t n_rnn, const int32_t* blk_nets, const int32_t* blk_range, int32_t n_blocks,
+                    const int32_t* order, const double* serves, int32_t n, int32_t max_steps, float* hc_scratch,
+                    int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
+                    const PlayRec* rec, void* stream) {
+    PM_REQUIRE(n >= 0 && n_blocks >= 0 && n_qnet >= 0 && n_rnn >= 0 && max_steps >= 0, PM_E_SIZE,
+               "%s: n=%d n_blocks=%d n_qnet=%d n_rnn=%d max_steps=%d", who, n, n_blocks, n_qnet, n_rnn, max_steps);
+    if (rec) {
+        PM_REQUIRE(rec->n_rec >= 0 && (rec->n_rec == 0 || rec->cap > 0), PM_E_SIZE, "%s: n_rec=%d rec_cap=%d", who,
+                   rec->n_rec, rec->cap);
+        PM_REQUIRE(rec->n_rec == 0 || (rec->row && rec->f64 && rec->q && rec->i32), PM_E_ARG,
+                   "%s: null record buffer", who);
+    }
+    if (n_blocks == 0) return PM_OK;
+    PM_REQUIRE(p && blk_nets && blk_range && order && serves && hc_scratch && scoreA && scoreB && length && last && status,
+               PM_E_ARG, "%s: null buffer", who);
+    PM_REQUIRE(n_qnet == 0 || (w_qnet && (((uintptr_t)w_qnet) & 15) == 0), PM_E_ARG,
+               "%s: w_qnet must be non-null and 16-byte aligned", who);
+    PM_REQUIRE(n_rnn == 0 || (w_rnn && (((uintptr_t)w_rnn) & 15) == 0), PM_E_ARG,
+               "%s: w_rnn must be non-null and 16-byte aligned", who);
+    PM_REQUIRE((((uintptr_t)hc_scratch) & 15) == 0, PM_E_ARG, "%s: hc_scratch must be 16-byte aligned", who);
+    PM_REQUIRE(p->speed_scale_every > 0, PM_E_ARG, "%s: speed_scale_every must be > 0", who);
+    if (rec && rec->n_rec > 0)
+        hipLaunchKernelGGL((k_play_rnn<true, PlayRec>), dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p,
+                           w_qnet, n_qnet, w_rnn, n_rnn, blk_nets, blk_range, order, serves, n, max_steps, hc_scratch,
+                           scoreA, scoreB, length, last, status, *rec);
+    else
+        hipLaunchKernelGGL(k_play_rnn<false>, dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p, w_qnet,
+                           n_qnet, w_rnn, n_rnn, blk_nets, blk_range, order, serves, n, max_steps, hc_scratch, scoreA,
+                           scoreB, length, last, status);
+    PM_LAUNCHED("k_play_rnn");
+    return PM_OK;
+}
+
+}  // namespace
+
 extern "C" int pm_play_rnn(const pm_env_params* p, const float* w_qnet, int32_t n_qnet, const float* w_rnn,
                            int32_t n_rnn, const int32_t* blk_nets, const int32_t* blk_range, int32_t n_blocks,
                            const int32_t* order, const double* serves, int32_t n, int32_t max_steps, float* hc_scratch,
                            int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last, int32_t* status,
                            void* stream) {
-    PM_REQUIRE(n >= 0 && n_blocks >= 0 && n_qnet >= 0 && n_rnn >= 0 && max_steps >= 0, PM_E_SIZE,
-               "pm_play_rnn: n=%d n_blocks=%d n_qnet=%d n_rnn=%d max_steps=%d", n, n_blocks, n_qnet, n_rnn, max_steps);
-    if (n_blocks == 0) return PM_OK;
-    PM_REQUIRE(p && blk_nets && blk_range && order && serves && hc_scratch && scoreA && scoreB && length && last && status,
-               PM_E_ARG, "pm_play_rnn: null buffer");
-    PM_REQUIRE(n_qnet == 0 || (w_qnet && (((uintptr_t)w_qnet) & 15) == 0), PM_E_ARG,
-               "pm_play_rnn: w_qnet must be non-null and 16-byte aligned");
-    PM_REQUIRE(n_rnn == 0 || (w_rnn && (((uintptr_t)w_rnn) & 15) == 0), PM_E_ARG,
-               "pm_play_rnn: w_rnn must be non-null and 16-byte aligned");
-    PM_REQUIRE((((uintptr_t)hc_scratch) & 15) == 0, PM_E_ARG, "pm_play_rnn: hc_scratch must be 16-byte aligned");
-    PM_REQUIRE(p->speed_scale_every > 0, PM_E_ARG, "pm_play_rnn: speed_scale_every must be > 0");
-    hipLaunchKernelGGL(k_play_rnn, dim3(n_blocks), dim3(kPlayBlock), 0, pm_stream(stream), *p, w_qnet, n_qnet, w_rnn,
-                       n_rnn, blk_nets, blk_range, order, serves, n, max_steps, hc_scratch, scoreA, scoreB, length,
-                       last, status);
-    PM_LAUNCHED("k_play_rnn");
-    return PM_OK;
+    return play_rnn_launch("pm_play_rnn", p, w_qnet, n_qnet, w_rnn, n_rnn, blk_nets, blk_range, n_blocks, order, serves,
+                           n, max_steps, hc_scratch, scoreA, scoreB, length, last, status, nullptr, stream);
+}
+
+extern "C" int pm_play_rnn_rec(const pm_env_params* p, const float* w_qnet, int32_t n_qnet, const float* w_rnn,
+                               int32_t n_rnn, const int32_t* blk_nets, const int32_t* blk_range, int32_t n_blocks,
+                               const int32_t* order, const double* serves, int32_t n, int32_t max_steps,
+                               float* hc_scratch, int32_t* scoreA, int32_t* scoreB, int32_t* length, int8_t* last,
+                               int32_t* status, const int32_t* rec_row, int32_t n_rec, int32_t rec_cap, double* rec_f64,
+                               float* rec_q, int32_t* rec_i32, void* stream) {
+    const PlayRec rec{rec_row, n_rec, rec_cap, rec_f64, rec_q, rec_i32};
+    return play_rnn_launch("pm_play_rnn_rec", p, w_qnet, n_qnet, w_rnn, n_rnn, blk_nets, blk_range, n_blocks, order,
+                           serves, n, max_steps, hc_scratch, scoreA, scoreB, length, last, status, &rec, stream);
 }

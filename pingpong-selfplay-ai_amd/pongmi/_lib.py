@@ -37,7 +37,7 @@ PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
-ABI_VERSION = 24
+ABI_VERSION = 25
 PM_TIMER_ACTENV, PM_TIMER_LEARN, PM_TIMER_RNN_ACT, PM_TIMER_ENV_STEP, PM_TIMER_ROLLOUT, PM_TIMER_DRQN = 0, 1, 2, 3, 4, 5
 PM_TIMER_LEARN_MULTI, PM_TIMER_N = 6, 7
 PM_ROLL_HEADS = 264
@@ -140,6 +140,12 @@ _SIGS = {
     "pm_play_rnn": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p,
                             c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pm_play_rnn_scratch_bytes": (ctypes.c_size_t, [c_i32]),
+    "pm_play_rec": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_void_p, c_void_p,
+                            c_void_p, c_void_p]),
+    "pm_play_rnn_rec": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                                c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pm_rollout": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64, c_u64, c_u64, c_i32,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_per_build": (c_i32, [c_void_p, c_i64, c_float, c_void_p, c_void_p]),

@@ -10,6 +10,10 @@ pongmi.tournament (QNet / ball-follower pairs).
 
 play_rnn is the same for pairs with a QNetRNN player (pm_play_rnn, csrc/pm_playrnn.hip): the
 block's RNN sides take one block-wide K5 step per tick, their (h, c) per column in a device scratch.
+
+Both take record=[arena, ...]: those arenas' episodes come back tick by tick as
+pongmi.record.MatchRecord (pm_play_rec / pm_play_rnn_rec, the kernels' recording instantiations);
+without it the launch is the plain kernel's.
 """
 import ctypes
 
@@ -19,6 +23,7 @@ import torch
 from . import _lib
 from ._lib import PM_QNET_NW, check, ptr, stream_ptr
 from .env import env_params
+from .record import MatchRecord
 
 FOLLOWER = -1
 RNN_BASE = -2        # play_rnn: QNetRNN net k has id RNN_BASE - k
@@ -76,21 +81,69 @@ def plan_blocks(netA, netB, per_block=None):
     return blk_nets, np.stack([lo, cnt], 1).astype(np.int32), order
 
 
-def play(env_kw, w_nets, netA, netB, serves, device="cuda", max_steps=1_000_000, per_block=None):
+class _Recording:
+    """The record buffers of one launch: rows in the order asked, record_ticks ticks each."""
+
+    def __init__(self, record, E, record_ticks):
+        """Checks `record` (arena indices, any order) on the host: before any device call."""
+        idx = np.asarray(list(record), dtype=object)
+        if any(not isinstance(k, (int, np.integer)) or isinstance(k, bool) for k in idx):
+            raise ValueError("record: arena indices (integers)")
+        self.arenas = idx.astype(np.int64)
+        if self.arenas.size and (self.arenas.min() < 0 or self.arenas.max() >= E):
+            raise ValueError(f"record: arena index outside [0, {E})")
+        if np.unique(self.arenas).size != self.arenas.size:
+            raise ValueError("record: an arena is listed twice")
+        self.cap = int(record_ticks)
+        if self.cap <= 0:
+            raise ValueError("record_ticks must be positive")
+        self.rows = np.full(E, -1, np.int32)
+        self.rows[self.arenas] = np.arange(self.arenas.size, dtype=np.int32)
+
+    def alloc(self, dev):
+        n = self.arenas.size
+        self.d_rows = torch.from_numpy(self.rows).to(dev)
+        self.f64 = torch.empty((n, self.cap, 7), dtype=torch.float64, device=dev)
+        self.q = torch.empty((n, self.cap, 2, 3), dtype=torch.float32, device=dev)
+        self.i32 = torch.empty((n, self.cap, 5), dtype=torch.int32, device=dev)
+
+    def args(self):
+        return (ptr(self.d_rows), int(self.arenas.size), self.cap, ptr(self.f64), ptr(self.q), ptr(self.i32))
+
+    def records(self, env_kw, idA, idB, serves, length):
+        """One MatchRecord per asked arena. Only the ticks an episode has are copied back."""
+        idA, idB = np.asarray(idA).reshape(-1), np.asarray(idB).reshape(-1)
+        F = np.minimum(length[self.arenas], self.cap).astype(np.int64)
+        dev = self.f64.device
+        stored = torch.arange(self.cap, device=dev)[None, :] < torch.from_numpy(F).to(dev)[:, None]
+        f64, q, i32 = (t[stored].cpu().numpy() for t in (self.f64, self.q, self.i32))  # rows back to back
+        lo = np.concatenate([[0], np.cumsum(F)])
+        return [MatchRecord.from_ticks(env_kw, (int(idA[i]), int(idB[i])), serves[i], int(length[i]),
+                                       f64[lo[r]:lo[r + 1]], q[lo[r]:lo[r + 1]], i32[lo[r]:lo[r + 1]])
+                for r, i in enumerate(self.arenas.tolist())]
+
+
+def play(env_kw, w_nets, netA, netB, serves, device="cuda", max_steps=1_000_000, per_block=None, record=None,
+         record_ticks=4096):
     """Play one greedy episode per arena. w_nets: effective weights [nets, PM_QNET_NW] (or None when
     every id is FOLLOWER); netA / netB: per-arena net ids; serves [E, 3] (vx, vy, spin).
     Returns host arrays (scoreA int32 [E], scoreB int32 [E], length int32 [E], last int8 [E]:
-    sign(rB - rA) of the final tick)."""
-    lib = _lib.load()
-    dev = torch.device(device)
+    sign(rB - rA) of the final tick).
+    record: arena indices (any order, no duplicates) whose episodes are also returned tick by tick, as
+    a fifth value: a list of MatchRecord in that order, each holding at most record_ticks ticks (the
+    players named by their net ids)."""
     serves = np.ascontiguousarray(np.asarray(serves, np.float64).reshape(-1, 3))
     E = serves.shape[0]
+    rec = None if record is None else _Recording(record, E, record_ticks)
+    lib = _lib.load()
+    dev = torch.device(device)
     sA = torch.zeros(E, dtype=torch.int32, device=dev)
     sB = torch.zeros(E, dtype=torch.int32, device=dev)
     length = torch.full((E,), -1, dtype=torch.int32, device=dev)
     last = torch.zeros(E, dtype=torch.int8, device=dev)
     if E == 0:
-        return sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy()
+        out = (sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy())
+        return out if rec is None else out + ([],)
     blk_nets, blk_range, order = plan_blocks(netA, netB, per_block)
     if w_nets is None:
         w = torch.zeros((1, PM_QNET_NW), dtype=torch.float32, device=dev)
@@ -109,15 +162,21 @@ def play(env_kw, w_nets, netA, netB, serves, device="cuda", max_steps=1_000_000,
     # the kernel bounds a wave's ticks over all its slots: max_steps per episode x slots per column
     per_col = -(-int(blk_range[:, 1].max()) // COLUMNS)
     wave_steps = min(int(max_steps) * per_col + per_col, 2**31 - 1)
-    check(lib.pm_play(ctypes.byref(prm), ptr(w), n_nets, ptr(d_int), ptr(d_int[2 * nb:]), nb, ptr(d_int[4 * nb:]),
-                      ptr(d_serves), E, wave_steps, ptr(sA), ptr(sB), ptr(length), ptr(last), ptr(status),
-                      stream_ptr()), "pm_play")
+    if rec is None:
+        check(lib.pm_play(ctypes.byref(prm), ptr(w), n_nets, ptr(d_int), ptr(d_int[2 * nb:]), nb, ptr(d_int[4 * nb:]),
+                          ptr(d_serves), E, wave_steps, ptr(sA), ptr(sB), ptr(length), ptr(last), ptr(status),
+                          stream_ptr()), "pm_play")
+    else:
+        rec.alloc(dev)
+        check(lib.pm_play_rec(ctypes.byref(prm), ptr(w), n_nets, ptr(d_int), ptr(d_int[2 * nb:]), nb,
+                              ptr(d_int[4 * nb:]), ptr(d_serves), E, wave_steps, ptr(sA), ptr(sB), ptr(length),
+                              ptr(last), ptr(status), *rec.args(), stream_ptr()), "pm_play_rec")
     out = (sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy())
     st = int(status.item())
     if st or (out[2] < 0).any():
         raise RuntimeError(f"pm_play: {int((out[2] < 0).sum())} arenas did not finish within {max_steps} steps "
                            f"({st} invalid ids or cut episodes)")
-    return out
+    return out if rec is None else out + (rec.records(env_kw, netA, netB, serves, out[2]),)
 
 
 def rnn_id(k):
@@ -125,22 +184,26 @@ def rnn_id(k):
     return RNN_BASE - k
 
 
-def play_rnn(env_kw, w_qnet, w_rnn, idA, idB, serves, device="cuda", max_steps=1_000_000, per_block=None):
+def play_rnn(env_kw, w_qnet, w_rnn, idA, idB, serves, device="cuda", max_steps=1_000_000, per_block=None, record=None,
+             record_ticks=4096):
     """Play one greedy episode per arena, at least one QNetRNN on each pair. w_qnet: effective QNet
     weights [nets, PM_QNET_NW] or None; w_rnn: effective QNetRNN weights [nets, PM_RNN_NW]
     (pongmi.rnn.fold); idA / idB: per-arena player ids (>= 0 QNet, FOLLOWER, rnn_id(k) QNetRNN k);
     serves [E, 3] (vx, vy, spin). Every episode starts from a zero hidden state. Returns host arrays
-    (scoreA int32 [E], scoreB int32 [E], length int32 [E], last int8 [E]) as play does."""
-    lib = _lib.load()
-    dev = torch.device(device)
+    (scoreA int32 [E], scoreB int32 [E], length int32 [E], last int8 [E]) as play does, and with
+    record=[arena, ...] the list of MatchRecord as play does (players named by their ids)."""
     serves = np.ascontiguousarray(np.asarray(serves, np.float64).reshape(-1, 3))
     E = serves.shape[0]
+    rec = None if record is None else _Recording(record, E, record_ticks)
+    lib = _lib.load()
+    dev = torch.device(device)
     sA = torch.zeros(E, dtype=torch.int32, device=dev)
     sB = torch.zeros(E, dtype=torch.int32, device=dev)
     length = torch.full((E,), -1, dtype=torch.int32, device=dev)
     last = torch.zeros(E, dtype=torch.int8, device=dev)
     if E == 0:
-        return sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy()
+        out = (sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy())
+        return out if rec is None else out + ([],)
     if per_block is None:
         per_block = min(MAX_SLOTS, COLUMNS * max(1, -(-E // (COLUMNS * TARGET_BLOCKS_RNN))))
     blk_nets, blk_range, order = plan_blocks(idA, idB, per_block)
@@ -168,12 +231,19 @@ def play_rnn(env_kw, w_qnet, w_rnn, idA, idB, serves, device="cuda", max_steps=1
     # the kernel bounds a block's ticks over all its slots: max_steps per episode x slots per column
     per_col = -(-int(blk_range[:, 1].max()) // COLUMNS)
     block_steps = min(int(max_steps) * per_col + per_col, 2**31 - 1)
-    check(lib.pm_play_rnn(ctypes.byref(prm), ptr(wq), n_qnet, ptr(wr), n_rnn, ptr(d_int), ptr(d_int[2 * nb:]), nb,
-                          ptr(d_int[4 * nb:]), ptr(d_serves), E, block_steps, ptr(scratch), ptr(sA), ptr(sB),
-                          ptr(length), ptr(last), ptr(status), stream_ptr()), "pm_play_rnn")
+    if rec is None:
+        check(lib.pm_play_rnn(ctypes.byref(prm), ptr(wq), n_qnet, ptr(wr), n_rnn, ptr(d_int), ptr(d_int[2 * nb:]), nb,
+                              ptr(d_int[4 * nb:]), ptr(d_serves), E, block_steps, ptr(scratch), ptr(sA), ptr(sB),
+                              ptr(length), ptr(last), ptr(status), stream_ptr()), "pm_play_rnn")
+    else:
+        rec.alloc(dev)
+        check(lib.pm_play_rnn_rec(ctypes.byref(prm), ptr(wq), n_qnet, ptr(wr), n_rnn, ptr(d_int), ptr(d_int[2 * nb:]),
+                                  nb, ptr(d_int[4 * nb:]), ptr(d_serves), E, block_steps, ptr(scratch), ptr(sA),
+                                  ptr(sB), ptr(length), ptr(last), ptr(status), *rec.args(), stream_ptr()),
+              "pm_play_rnn_rec")
     out = (sA.cpu().numpy(), sB.cpu().numpy(), length.cpu().numpy(), last.cpu().numpy())
     st = int(status.item())
     if st or (out[2] < 0).any():
         raise RuntimeError(f"pm_play_rnn: {int((out[2] < 0).sum())} arenas did not finish within {max_steps} steps "
                            f"({st} invalid ids or cut episodes)")
-    return out
+    return out if rec is None else out + (rec.records(env_kw, idA, idB, serves, out[2]),)

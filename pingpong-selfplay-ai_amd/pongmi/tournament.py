@@ -17,6 +17,9 @@ the serve the reference's would, and all episodes run at once:
     state, HardcodedBallFollower through the same comparison as :207-228 (float32, numpy 2
     semantics). Both paths give the same episodes.
 
+play_matches(..., record=[episode, ...]) also returns those episodes tick by tick (the fused paths'
+recording kernels, pongmi.record.MatchRecord), to be watched with pongmi.viewer.replay.
+
 load_model_universal keeps the reference's checkpoint key order, its legacy fc.* -> dueling mapping
 (:144-168) and strictness, and loads with torch.load(weights_only=True). The returned frames have
 the reference's columns and order (match records: pair-major, episode 1..E; summary: by win_rate).
@@ -119,39 +122,63 @@ class _Player:
         out.index_copy_(0, rows, a.to(out.dtype))
 
 
-def play_matches(env_params, models, plan, device="cuda", rng=None, max_steps=1_000_000, rnn="fused"):
+def play_matches(env_params, models, plan, device="cuda", rng=None, max_steps=1_000_000, rnn="fused", record=None,
+                 record_ticks=4096):
     """Play every episode of `plan` at once. models: name -> (module or "HardcodedAgent", type);
     plan: [(name_A, name_B, episodes)] in the order the reference plays them (its serves are drawn
     from `rng` / the global random stream in that order, one env.reset() per episode).
     Episodes between QNet / ball-follower players run in the match megakernel (K8, pongmi.play);
     episodes with a QNetRNN player in its QNetRNN form (pm_play_rnn) or, with rnn="stepped", all their
     arenas in lockstep (K5 + K1 per tick); both give the same episodes.
-    Returns [(name_A, name_B, score_A, score_B)] per episode, in plan order."""
+    Returns [(name_A, name_B, score_A, score_B)] per episode, in plan order.
+    record: episode indices into that list (any order, no duplicates); with it the return value is
+    (results, {index: MatchRecord}), each record at most record_ticks ticks long and carrying the
+    participants' names. Only the fused paths record."""
     if rnn not in ("fused", "stepped"):
         raise ValueError(f"rnn must be 'fused' or 'stepped', not {rnn!r}")
+    if record is not None and rnn == "stepped":
+        raise ValueError("record needs rnn='fused': the stepped path keeps no ticks")
     rng = _pyrandom if rng is None else rng
     env_kw = {k: v for k, v in dict(env_params).items() if k not in ("render_size", "enable_render")}
     cfg = env_config(**env_kw)
     eps = [(a, b) for a, b, e in plan for _ in range(int(e))]
     n = len(eps)
+    if record is not None:
+        record = [int(k) for k in record]
+        if len(set(record)) != len(record) or any(not 0 <= k < n for k in record):
+            raise ValueError(f"record: distinct episode indices in [0, {n})")
     if n == 0:
-        return []
+        return [] if record is None else ([], {})
     serves = np.array([draw_serve(rng, cfg) for _ in range(n)], np.float64).reshape(n, 3)
     score = np.zeros((n, 2), np.int64)
     recurrent = {nm for nm, (_, typ) in models.items() if typ == "QNetRNN"}
     stepped = np.array([a in recurrent or b in recurrent for a, b in eps], bool)
+    records, wanted = {}, set(record or ())
+
+    def run(fn, part):
+        """Scores of the episodes `part` (indices into eps) played by fn. With `record`, fn is also
+        given the recorded ones among them (by their index within `part`) and their MatchRecords
+        are kept, the net ids replaced by the participants' names."""
+        part_eps = [eps[k] for k in part]
+        if record is None:
+            return fn(env_kw, models, part_eps, serves[part], device, max_steps)
+        local = [j for j, k in enumerate(part) if k in wanted]
+        score, recs = fn(env_kw, models, part_eps, serves[part], device, max_steps, local, record_ticks)
+        for j, rec in zip(local, recs):
+            rec.players = part_eps[j]
+            records[int(part[j])] = rec
+        return score
     if (~stepped).any():
-        score[~stepped] = _play_fused(env_kw, models, [eps[k] for k in np.nonzero(~stepped)[0]], serves[~stepped],
-                                      device, max_steps)
+        score[~stepped] = run(_play_fused, np.nonzero(~stepped)[0])
     if stepped.any():
-        play_recurrent = _play_fused_rnn if rnn == "fused" else _play_stepped
-        score[stepped] = play_recurrent(env_kw, models, [eps[k] for k in np.nonzero(stepped)[0]], serves[stepped],
-                                        device, max_steps)
-    return [(a, b, int(score[k, 0]), int(score[k, 1])) for k, (a, b) in enumerate(eps)]
+        score[stepped] = run(_play_fused_rnn if rnn == "fused" else _play_stepped, np.nonzero(stepped)[0])
+    results = [(a, b, int(score[k, 0]), int(score[k, 1])) for k, (a, b) in enumerate(eps)]
+    return results if record is None else (results, {k: records[k] for k in record})
 
 
-def _play_fused(env_kw, models, eps, serves, device, max_steps):
-    """QNet / ball-follower episodes in the match megakernel: [E, 2] final scores."""
+def _play_fused(env_kw, models, eps, serves, device, max_steps, record=None, record_ticks=4096):
+    """QNet / ball-follower episodes in the match megakernel: [E, 2] final scores (and, with record,
+    the MatchRecords of those episodes)."""
     from .play import FOLLOWER, play
     ids, weights = {}, []
     for nm in dict.fromkeys([x for ab in eps for x in ab]):
@@ -162,12 +189,15 @@ def _play_fused(env_kw, models, eps, serves, device, max_steps):
             ids[nm] = len(weights)
             weights.append(_qnet.fold(module.packed().to(device), _lib.PM_FOLD_EVAL)[0])
     w = torch.stack(weights) if weights else None
-    sA, sB, _, _ = play(env_kw, w, [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps)
-    return np.stack([sA, sB], 1)
+    out = play(env_kw, w, [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps,
+               record=record, record_ticks=record_ticks)
+    score = np.stack([out[0], out[1]], 1)
+    return score if record is None else (score, out[4])
 
 
-def _play_fused_rnn(env_kw, models, eps, serves, device, max_steps):
-    """Episodes with a QNetRNN player in the match megakernel's QNetRNN form: [E, 2] final scores."""
+def _play_fused_rnn(env_kw, models, eps, serves, device, max_steps, record=None, record_ticks=4096):
+    """Episodes with a QNetRNN player in the match megakernel's QNetRNN form: [E, 2] final scores (and,
+    with record, the MatchRecords of those episodes)."""
     from .play import FOLLOWER, play_rnn, rnn_id
     ids, wq, wr = {}, [], []
     for nm in dict.fromkeys([x for ab in eps for x in ab]):
@@ -180,9 +210,11 @@ def _play_fused_rnn(env_kw, models, eps, serves, device, max_steps):
         else:
             ids[nm] = len(wq)
             wq.append(_qnet.fold(module.packed().to(device), _lib.PM_FOLD_EVAL)[0])
-    sA, sB, _, _ = play_rnn(env_kw, torch.stack(wq) if wq else None, torch.stack(wr) if wr else None,
-                            [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps)
-    return np.stack([sA, sB], 1)
+    out = play_rnn(env_kw, torch.stack(wq) if wq else None, torch.stack(wr) if wr else None,
+                   [ids[a] for a, _ in eps], [ids[b] for _, b in eps], serves, device, max_steps,
+                   record=record, record_ticks=record_ticks)
+    score = np.stack([out[0], out[1]], 1)
+    return score if record is None else (score, out[4])
 
 
 def _play_stepped(env_kw, models, eps, serves, device, max_steps):

@@ -1,12 +1,20 @@
-"""Viewer hook: a PongEnv2P-shaped, read-only view of one arena of device state.
+"""Viewer hooks: a PongEnv2P-shaped, read-only view of one arena of device state, or of one frame
+of a recorded match.
 
 The reference's viewers (tests/test_viewer_v2.py:134-187, tests/pingpong_viewer/**) step their own
 PongEnv2P and read ball_x / ball_y / ball_vx / ball_vy / spin / top_paddle_x / bottom_paddle_x /
 scoreA / scoreB / paddle_width / world_ball_radius off it. The drop-in envs.my_pong_env_2p.PongEnv2P
 already runs them unchanged on a one-arena device batch. ArenaView is the other direction: it looks
-at arena `index` of a batch that something else is stepping, such as a PongEnv2PBatch, the self-play
-learners or a tournament batch, so a viewer can watch training or a match live. Each refresh() is
-one 80-byte device-to-host copy; the arenas stay in HBM.
+at arena `index` of a batch that something else is stepping, such as a PongEnv2PBatch or the
+self-play learners, so a viewer can watch training live. Each refresh() is one 80-byte
+device-to-host copy; the arenas stay in HBM.
+
+Matches (evaluation, the tournament, the arena) are not stepped batches: the match megakernels play
+every episode from serve to final score inside one launch, the arenas in registers. They are watched
+afterwards. pongmi.tournament.play_matches(..., record=[episode, ...]) (or pongmi.play.play /
+play_rnn with record=) returns the chosen episodes as pongmi.record.MatchRecord, every tick as the
+kernel played it; replay(record) yields one RecordView per frame, with ArenaView's attributes and
+frame(), plus the actions and q values of the tick that led to the frame.
 
 frame() rasterises what PongEnv2P.render (envs/my_pong_env_2p.py:265-306) draws into an RGB numpy
 array: black field, white ball of radius 8 px with the red spin cross, green 10 px paddles. It needs
@@ -89,6 +97,58 @@ class ArenaView:
         pygame.surfarray.blit_array(self._screen, img.transpose(1, 0, 2))
         pygame.display.flip()
         return img
+
+
+class RecordView:
+    """Frame `t` of a MatchRecord as the attributes a PongEnv2P viewer reads (seek() to move).
+    Frame 0 is the reset state; frame t > 0 is the state after tick t - 1, and `actions` / `q` are
+    that tick's (None on frame 0)."""
+
+    def __init__(self, record, t=0, render_size=None):
+        from .env import env_config
+        cfg = env_config(**record.env_kw)
+        self.record = record
+        self.index = 0
+        self.paddle_width = float(cfg["paddle_width"])
+        self.world_ball_radius = float(cfg["world_ball_radius"])
+        self.max_score = int(cfg["max_score"])
+        self.render_size = int(render_size or cfg.get("render_size", 400))
+        self.spin_angle = 0.0
+        self.seek(t)
+
+    def seek(self, t):
+        t = int(t)
+        if not 0 <= t <= self.record.frames:
+            raise IndexError(f"frame {t} of {self.record.frames + 1}")
+        self.t = t
+        for k, name in enumerate(_F64):
+            setattr(self, name, float(self.record.states[t, k]))
+        self.scoreA, self.scoreB = (int(v) for v in self.record.scores[t])
+        self.bounce_count = int(self.record.bounces[t])
+        self.actions = None if t == 0 else tuple(int(v) for v in self.record.actions[t - 1])
+        self.q = None if t == 0 else self.record.q[t - 1].copy()
+        return self
+
+    def refresh(self):
+        return self
+
+    def obs(self):
+        return self.record.obs(self.t)
+
+    def frame(self, advance_spin=True):
+        """RGB uint8 [render_size, render_size, 3] of what render() draws for this frame."""
+        if advance_spin:
+            self.spin_angle += self.spin
+        return draw_frame(self.ball_x, self.ball_y, self.top_paddle_x, self.bottom_paddle_x, self.paddle_width,
+                          self.spin_angle, self.render_size)
+
+
+def replay(record, render_size=None):
+    """Yield a RecordView of every frame of `record` in order (F + 1 frames; the same object, moved
+    on, so its spin_angle accumulates over frame() calls as a live viewer's does)."""
+    view = RecordView(record, 0, render_size)
+    for t in range(record.frames + 1):
+        yield view.seek(t)
 
 
 def draw_frame(ball_x, ball_y, top_x, bot_x, paddle_width, spin_angle, size):
