@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 25
+#define PM_ABI_VERSION 26
 
 #define PM_OK 0
 #define PM_E_ARG (-1)     /* null / inconsistent argument */
@@ -581,8 +581,29 @@ typedef struct pm_selfplay {
                                 since modelB's feature layers last changed, so frow is current; then
                                 pm_selfplay_step_multi runs updates 1..U-1 as ONE single-workgroup launch
                                 (k_learn_multi) instead of 3 launches per update */
-    int32_t _pad1;
+    int32_t gB_ready;        /* host-set, as frow_ready (ABI 26): nonzero = gB holds, tile by tile, modelB's greedy
+                                action for the observations now in obsB or the sentinel, i.e. the last launch
+                                that wrote them was a pm_selfplay_learn_act for which pm_selfplay_act_ahead
+                                answers 1. Zero after anything else that changes the observations, the
+                                opponents or modelB (pm_selfplay_act_part A / ALL, prepare, init): featB is
+                                then current for every tile and pm_selfplay_actenv reads it */
+    int8_t *gB;              /* nullable [n] (ABI 26): modelB's greedy action (0..2) for the observations now in
+                                obsB, stored by the feature blocks of pm_selfplay_learn_act once the learner
+                                has published the next step's acting heads (gheads); pm_selfplay_actenv then
+                                reads one byte per arena instead of 256 B of featB and runs no head pass.
+                                PM_GB_NONE in all 32 arenas of a feature tile: that tile's hand-off timed out,
+                                its features are in featB as before (the results are the same bits).
+                                Fill with PM_GB_NONE before the first step. Not sp->aB: aB stays "the action
+                                taken last step". Needs featB, gheads, fuse_apply, no frow */
+    uint64_t *gheads;        /* nullable [PM_GHEADS_LEN], zero-filled before the first step (ABI 26): the
+                                learner -> feature blocks hand-off inside pm_selfplay_learn_act. Granule k < 260
+                                = (epoch tag << 32 | float bits) of folded acting head value k of the next
+                                step (Wh [4][64] | bh [4]); word PM_GHEADS_EPOCH = the epoch, bumped by the
+                                learner at the end of every launch that publishes */
 } pm_selfplay;
+#define PM_GB_NONE 3
+#define PM_GHEADS_EPOCH 260
+#define PM_GHEADS_LEN 264
 
 /* Limits: 1 <= batch <= PM_MAX_BATCH (one learner workgroup), batch < n <= cap (every vector step
  * pushes n > batch transitions, which keeps the tracked max priority exact), n_pool <= 4096. */
@@ -643,6 +664,17 @@ int pm_selfplay_act_part(const pm_selfplay* sp, int32_t part, void* stream);
 int pm_selfplay_learn_act(const pm_selfplay* sp, void* stream);
 int pm_selfplay_actenv(const pm_selfplay* sp, void* stream);
 int pm_selfplay_step_overlap(const pm_selfplay* sp, void* stream);
+/* Actions ahead (ABI 26). 1 if pm_selfplay_learn_ex(sp, mode, with_act) would leave modelB's greedy actions
+ * for the next step in sp->gB instead of its features in sp->featB (pm_selfplay_learn_act = mode
+ * PM_UPD_FIRST | PM_UPD_LAST with the act; pm_selfplay_step_overlap ends with it): the fused U = 1 step
+ * (fuse_apply, both mode bits, with_act) with featB, gB and gheads set, frow NULL, and a learner grid
+ * whose feature blocks are all resident beside the learner with at most two 32-arena tiles per wave
+ * (up to configs[2]'s 65 536 arenas and somewhat above on a 256-CU device); 0 otherwise, and always
+ * with PONGMI_ACT_AHEAD=0 in the environment (read per call: the A/B switch). The caller sets
+ * sp->gB_ready to this answer for the next pm_selfplay_actenv, and to 0 once anything else rewrote the
+ * observations or the networks. Test hook: PONGMI_AHEAD_FORCE_TIMEOUT=1 makes the feature blocks' poll
+ * for the heads expire at once (every tile then takes the featB path). */
+int pm_selfplay_act_ahead(const pm_selfplay* sp, int32_t mode, int32_t with_act);
 
 /* Replay ratio: U >= 1 double-DQN updates per vector step. The reference trains once per env step
  * (train_iterative.py:243-244), i.e. once per pushed transition; U = n keeps that ratio for n arenas.

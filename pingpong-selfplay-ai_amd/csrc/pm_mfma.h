@@ -585,6 +585,17 @@ __device__ __forceinline__ void store_f4_sc1(__amdgpu_buffer_rsrc_t r, int byte_
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(&v), r, byte_off, 0, 16 /* sc1 */);
 }
+// One tile's pre-ReLU layer-2 accumulators into feat (the layout above).
+__device__ __forceinline__ void feat_store(float* __restrict__ feat, int tl, int lane, const f32x16 (&c2)[2]) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(feat, (short)0, 0x7fffffff, 0x00020000);
+    const int off = (tl * 8 * 64 + lane) * 16;  // bytes; < 2 GB for n < 2^23 arenas
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        store_f4_sc1(rs, off + k * 64 * 16, make_float4(c2[0][4 * k], c2[0][4 * k + 1], c2[0][4 * k + 2], c2[0][4 * k + 3]));
+        store_f4_sc1(rs, off + (4 + k) * 64 * 16,
+                     make_float4(c2[1][4 * k], c2[1][4 * k + 1], c2[1][4 * k + 2], c2[1][4 * k + 3]));
+    }
+}
 __device__ __forceinline__ void feat_tiles(float* lw, const float* __restrict__ w, const float* __restrict__ obs, int n,
                                            int t0, int t1, float* __restrict__ feat) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
@@ -599,14 +610,7 @@ __device__ __forceinline__ void feat_tiles(float* lw, const float* __restrict__ 
         if (tn < t1) tile_inputs(obs + (size_t)min(tn * 32 + (lane & 31), n - 1) * 7, lane >> 5, xn);
         f32x16 c2[2];
         tile_hidden(lw, xs, lane, c2);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(feat, (short)0, 0x7fffffff, 0x00020000);
-        const int off = (tl * 8 * 64 + lane) * 16;  // bytes; < 2 GB for n < 2^23 arenas
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            store_f4_sc1(rs, off + k * 64 * 16, make_float4(c2[0][4 * k], c2[0][4 * k + 1], c2[0][4 * k + 2], c2[0][4 * k + 3]));
-            store_f4_sc1(rs, off + (4 + k) * 64 * 16,
-                         make_float4(c2[1][4 * k], c2[1][4 * k + 1], c2[1][4 * k + 2], c2[1][4 * k + 3]));
-        }
+        feat_store(feat, tl, lane, c2);
 #pragma unroll
         for (int k = 0; k < 4; ++k) xs[k] = xn[k];
     }

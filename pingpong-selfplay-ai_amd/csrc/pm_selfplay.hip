@@ -33,6 +33,11 @@ static __device__ unsigned long long pm_diag_side[4][1024];
     do {                                                                         \
         if (threadIdx.x == 0 && (sb) < 1024) pm_diag_side[(k)][(sb)] = (v);      \
     } while (0)
+// latest time over the blocks of one role reaching a point (thread 0's atomic max, no barrier)
+#define PM_STAMP_MAX_NB(slot)                                                                              \
+    do {                                                                                                   \
+        if (threadIdx.x == 0) atomicMax(&pm_diag_buf[(slot)], (unsigned long long)__builtin_amdgcn_s_memrealtime()); \
+    } while (0)
 #define PM_ENV_STAMP(k, blk)                                                                   \
     do {                                                                                       \
         asm volatile("" ::: "memory");                                                         \
@@ -46,6 +51,9 @@ static __device__ unsigned long long pm_diag_side[4][1024];
 #else
 #define PM_SIDE(k, sb, v) \
     do {                  \
+    } while (0)
+#define PM_STAMP_MAX_NB(slot) \
+    do {                      \
     } while (0)
 #define PM_ENV_STAMP(k, blk) \
     do {                     \
@@ -133,6 +141,94 @@ constexpr int kFeatTilesAct = 8, kFeatTilesLearn = 16;
 #endif
 constexpr bool kEnvWTRows = (PM_ENV_WT & 1) != 0, kEnvWTState = (PM_ENV_WT & 2) != 0, kEnvWTObs = (PM_ENV_WT & 4) != 0;
 __host__ __device__ inline int feat_ntiles(int n) { return (n + 31) / 32; }
+
+// Actions ahead (ABI 26): the fused U = 1 learner launch hands k_actenv modelB's greedy ACTIONS for the
+// next step (sp.gB, one byte per arena) instead of its 64 features (sp.featB, 256 B). The features
+// crossed the launch boundary only because the acting heads were not final when the feature blocks
+// computed them; they are final inside the same launch, right after the learner's Adam. So the learner
+// publishes the 260 folded acting head values as tagged 8-byte granules (sp.gheads; push_publish's
+// idiom: value and epoch tag in one agent-scope store, the data is the flag), the feature blocks keep
+// their tiles' layer-2 accumulators in registers (at most two tiles per wave), poll for the granules
+// after their last tile, and run the same tile_heads + argmax3 on the same accumulators with the same
+// head values k_actenv's env blocks would: the same bits. A poll that expires (bounded) stores the
+// block's tiles to featB as before and PM_GB_NONE to their gB; an env block's wave that finds the
+// sentinel in a tile takes that tile from featB. The epoch (gheads word PM_GHEADS_EPOCH) is read by
+// every block at its start and bumped by the learner at its very end, so a tag is never reused by a
+// later launch (checkpoint restores included); a feature block dispatched after the learner ended
+// (never when the grid fits the device: launch_learn checks) would wait for a tag nobody publishes
+// and fall back.
+__device__ __forceinline__ bool gb_current(const pm_selfplay& sp) {
+    return sp.featB && sp.gB && sp.gB_ready && !sp.frow;
+}
+__device__ __forceinline__ uint32_t* gh_epoch(const pm_selfplay& sp) {
+    return reinterpret_cast<uint32_t*>(sp.gheads + PM_GHEADS_EPOCH);
+}
+constexpr int kAheadPollMax = 20000;  // as kPushPollMax (~20 ms)
+__device__ __forceinline__ void gh_publish(const pm_selfplay& sp, int k, uint32_t tag, float v) {
+    __hip_atomic_store(sp.gheads + k, ((uint64_t)tag << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// k_learn's feature block in a launch with actions ahead: tiles [t0, t1) of 32 arenas, at most two per
+// wave (t1 - t0 <= 2 waves: launch_learn checks). feat_tiles' tile code (the same accumulators), then
+// the hand-off described above. Block-wide, every barrier block-uniform.
+struct FeatAheadSmem {
+    float lw[kLwFloats];  // modelB's acting fragment image (the feature layers)
+    float hf[264];        // the next step's acting heads in F_H | F_BH fragment order, from the granules
+    int ok;               // every granule arrived
+};
+__device__ __forceinline__ void feat_tiles_ahead(const pm_selfplay& sp, FeatAheadSmem& sm, int t0, int t1, bool force_timeout) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, nw = blockDim.x >> 6;
+    stage_frags_lds(sp.w_B, sm.lw, t0);
+    const uint32_t tag = __hip_atomic_load(gh_epoch(sp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    const int tl[2] = {t0 + wave, t0 + wave + nw};
+    const bool has[2] = {tl[0] < t1, tl[1] < t1};  // wave-uniform; t1 - t0 <= 2 nw
+    float xs[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (has[k]) tile_inputs(sp.obsB + (size_t)min(tl[k] * 32 + (lane & 31), sp.n - 1) * 7, lane >> 5, xs[k]);
+    if (t == 0) sm.ok = 1;
+    __syncthreads();
+    f32x16 c2[2][2] = {};
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        if (has[k]) tile_hidden(sm.lw, xs[k], lane, c2[k]);
+    PM_STAMP_MAX_NB(68);
+    // the learner's granules: thread k < 256 takes the head value of fragment slot k (heads_to_frags'
+    // map), threads 256..259 the biases
+    if (t < 260) {
+        const int c = t & 3, r = (t >> 2) & 15, tt = (t >> 6) & 1, h = t >> 7;
+        const int src = t < 256 ? c * 64 + 32 * tt + rho(r) + 4 * h : t;
+        uint64_t g = 0;
+        bool got = false;
+        for (int it = 0; !force_timeout && it < kAheadPollMax; ++it) {
+            g = __hip_atomic_load(sp.gheads + src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((uint32_t)(g >> 32) == tag) { got = true; break; }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        if (got) sm.hf[t] = __uint_as_float((uint32_t)g);
+        else sm.ok = 0;
+    }
+    __syncthreads();
+    PM_STAMP_MAX_NB(69);
+    const bool ok = sm.ok != 0;  // block-uniform
+    // (one sweep of the head weights per tile: the sweeps' LDS reads, 1 KB per wave and step, bound this
+    // tail, ~18 tiles x 32 steps per CU; a two-tile sweep halves them but spilled at this kernel's
+    // 128-register cap)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!has[k]) continue;  // wave-uniform
+        const int arena = tl[k] * 32 + (lane & 31);
+        int a = PM_GB_NONE;
+        if (ok) {
+            float q[3];
+            tile_heads(sm.hf, c2[k], lane, q);
+            a = argmax3(q);
+        } else {
+            feat_store(sp.featB, tl[k], lane, c2[k]);
+        }
+        if (lane < 32 && arena < sp.n) sp.gB[arena] = (int8_t)a;
+    }
+}
 
 __global__ __launch_bounds__(kActBlock, 4) void k_act_sp(const pm_selfplay sp, int part) {
     __shared__ __attribute__((aligned(16))) ActSpShared sh;
@@ -351,7 +447,11 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
     PM_ENV_STAMP(0, blk);
     float xs[2][4];
     f32x16 fc2[2][2];  // featB: this wave's two tiles of modelB's features (computed ahead)
-    if (ACT && sp.featB) {
+    // actions ahead: gB holds the greedy action (or, tile-wise, the sentinel). Nothing is staged and
+    // there is no barrier; a kernel-argument condition, so block-uniform
+    const bool ahead = ACT && gb_current(sp);
+    if (ahead) {
+    } else if (ACT && sp.featB) {
         // heads only: F_H .. F_BH of the acting image (65 float4) -> LDS; the features from featB
         if (threadIdx.x < 65)
             reinterpret_cast<float4*>(lw + F_H)[threadIdx.x] =
@@ -381,7 +481,7 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
     const float er0 = sp.ep_reward[ii];
     Arena a = load_arena(sp.st, ii);
     const int aA = sp.aA[ii];
-    int aB = ACT ? 0 : sp.aB[ii];
+    int aB = ACT ? (ahead ? (int)sp.gB[ii] : 0) : sp.aB[ii];
     __builtin_amdgcn_sched_barrier(0);
     const float maxp = push_prio(size, cmaxp);  // max(prios) if buffer else 1.0 (:57)
     float* leaf = per_tree(sp.per_work, sp.cap).leaf;
@@ -405,7 +505,24 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
         asm volatile("" ::"v"(onext), "v"(svx), "v"(svy), "v"(sspn), "v"(eps_hit), "v"(eps_a));
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (ACT) {
+    if (ahead) {
+        // a tile whose hand-off timed out in the learner launch (all 32 arenas hold the sentinel): its
+        // features are in featB; heads straight from the acting image in global memory (the same
+        // values in the same order as the staged copy). Wave-uniform, no barrier.
+        const unsigned long long fb = __ballot(valid && aB == PM_GB_NONE);
+        if (fb) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                if (!(uint32_t)(fb >> (32 * k))) continue;  // wave-uniform
+                float q[3];
+                feat_load(sp.featB, blk * 8 + 2 * wv + k, lane, fc2[k]);
+                tile_heads(sp.w_B + PLAIN + F_H, fc2[k], lane, q);
+                if ((lane >> 5) == k) aB = argmax3(q);
+            }
+        }
+        if (!valid) aB = 0;  // lanes past n read arena n - 1's byte (possibly the sentinel); nothing of theirs is stored
+        PM_ENV_STAMP(7, blk);
+    } else if (ACT) {
         __syncthreads();  // the fragment image is staged (every load of the block has landed)
         PM_ENV_STAMP(7, blk);
         int act[2];
@@ -612,7 +729,10 @@ __device__ __forceinline__ void load_apply_inputs(const pm_selfplay& sp, ApplySm
 // in modelB's epsilon buffers), the next update's modelB heads with fresh noise (reset_noise, :142)
 // and targetB heads (eval mode: mu, :100), both in MFMA fragment order in learn_heads, plus that
 // update's noise. Block-wide; noise already in sm.nact / sm.ntrain.
-__device__ __forceinline__ void derive_weights(const pm_selfplay& sp, ApplySmem& sm) {
+// gh_on (actions ahead): the folded acting heads also go out as granules of tag gh_tag for this launch's
+// feature blocks, each from the thread that folded it (no barrier in front of the hand-off), before any
+// fragment write.
+__device__ __forceinline__ void derive_weights(const pm_selfplay& sp, ApplySmem& sm, bool gh_on = false, uint32_t gh_tag = 0) {
     const int t = threadIdx.x;
     float* lh = sp.learn_heads;
     // the three folds are independent: one pass on three 260-thread groups, one barrier, then the
@@ -621,6 +741,11 @@ __device__ __forceinline__ void derive_weights(const pm_selfplay& sp, ApplySmem&
     const int g = (t - 256) >> 8, u = (t - 256) & 255;
     if (t >= 256 && g == 0) {
         fold_heads_from(sm.hp, nullptr, sm.nact, PM_FOLD_TRAIN_FRESH, sm.heads[0], sp.paramsB + PM_QNET_EPS_OFF, u, 256);
+        if (gh_on) {  // fold_heads_from(tid u, 256 threads) wrote heads[0][u], and heads[0][256 + u] for u < 4
+            gh_publish(sp, u, gh_tag, sm.heads[0][u]);
+            if (u < 4) gh_publish(sp, 256 + u, gh_tag, sm.heads[0][256 + u]);
+            PM_STAMP_T(22, 256);
+        }
     } else if (t >= 256 && g == 1) {
         fold_heads_from(sm.hp, nullptr, sm.ntrain, PM_FOLD_TRAIN_FRESH, sm.heads[1], lh + 528, u, 256);
     } else if (t >= 256 && g == 2) {
@@ -694,7 +819,8 @@ __device__ __forceinline__ void apply_adam(const pm_selfplay& sp, ApplySmem& sm)
 }
 // mode (PM_UPD_*): FIRST commits the epsilon decay of the step's finished episodes, LAST the replay
 // and step counters (with U > 1 updates per step pm_selfplay_commit does that after the last one).
-__device__ __forceinline__ void apply_finish(const pm_selfplay& sp, ApplySmem& sm, const pm_ctrl& cs, int mode) {
+__device__ __forceinline__ void apply_finish(const pm_selfplay& sp, ApplySmem& sm, const pm_ctrl& cs, int mode,
+                                             bool gh_on = false, uint32_t gh_tag = 0) {
     const int t = threadIdx.x, nt = blockDim.x;
     const bool train = sm.g[kGradN + 1] > 0.5f;
     const int64_t ts = cs.train_steps + (train ? 1 : 0);
@@ -708,7 +834,7 @@ __device__ __forceinline__ void apply_finish(const pm_selfplay& sp, ApplySmem& s
         }
         __syncthreads();
     }
-    derive_weights(sp, sm);
+    derive_weights(sp, sm, gh_on, gh_tag);
     PM_STAMP(21);
     if (t == 0) {
         pm_ctrl* c = sp.ctrl;
@@ -1216,6 +1342,7 @@ union LearnShared {
     ActSharedLearn act;
     PushFwdSmem pf;
     TreeRefreshSmem tr;
+    FeatAheadSmem fa;
 };
 static_assert(sizeof(LearnShared) <= 160 * 1024, "k_learn LDS");
 
@@ -1236,9 +1363,11 @@ __device__ __forceinline__ void side_nap(int n) {
 // PG: the push rows as tagged granules (tr bit 3; a separate instantiation: the flag consumer's
 // branch beside the granule sweep made the compiler wait for every granule load in turn).
 template <bool PG>
-__global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chunkA, int chunkP, int mode, int tr, int ftiles, int sleepf) {
+__global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chunkA, int chunkP, int mode, int tr, int ftiles, int sleepf, int ahead) {
     __shared__ __attribute__((aligned(16))) LearnShared shm;
     // tr: bit 0 the tree-refresh block, bit 1 push_rows_fwd2, bit 2 the apply's noise in phase 2
+    // ahead: bit 0 actions ahead (the feature blocks store gB, the learner publishes the acting heads),
+    // bit 1 test hook: the feature blocks' poll for them expires at once
     const bool push2 = (tr & 2) != 0, late_noise = (tr & 4) != 0;
     const int tr_poll = (tr & 16) ? 0 : kTrPollMax;  // bit 4: test hook, the refresh block's poll times out at once
     constexpr bool pushg = PG;
@@ -1259,7 +1388,8 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
         if (fb >= 0) {  // block-uniform: modelB's features for the next step (sp.featB)
             if (sleepf & 2) side_nap(sleepf >> 8);
             const int t0 = fb * ftiles;
-            feat_tiles(shm.act.lw, sp.w_B, sp.obsB, sp.n, t0, min(t0 + ftiles, feat_ntiles(sp.n)), sp.featB);
+            if (ahead & 1) feat_tiles_ahead(sp, shm.fa, t0, min(t0 + ftiles, feat_ntiles(sp.n)), (ahead & 2) != 0);
+            else feat_tiles(shm.act.lw, sp.w_B, sp.obsB, sp.n, t0, min(t0 + ftiles, feat_ntiles(sp.n)), sp.featB);
             PM_STAMP_MAX(67);
             PM_SIDE(2, sb, __builtin_amdgcn_s_memrealtime());
             PM_SIDE(3, sb, 1ull | ((unsigned long long)(min(t0 + ftiles, feat_ntiles(sp.n)) - t0) << 16));
@@ -1301,6 +1431,7 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
     const int64_t id_l = t < B ? sp.idx[t] : 0;
     const float eps_v = t < 260 ? sp.learn_heads[528 + t] : 0.f;
     const uint32_t tr_tag = tr ? __hip_atomic_load(tr_epoch(sp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
+    const uint32_t gh_tag = (ahead & 1) ? __hip_atomic_load(gh_epoch(sp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u : 0u;
     // the rows k_env's forward blocks computed (hfeat [B][80]): sample t's Q block (floats 64..75,
     // phase 2's operands) global -> LDS (qv4 planes) here; its 64 features go global -> LDS below.
     // (Round 4 loaded it to registers: the compiler kept the float4[3] in scratch, a store that
@@ -1630,6 +1761,15 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
                 adam_one(sp, sm.ap, ksg, gsg);
             }
         }
+        // actions ahead: thread t < 260 owns both parameters (mu, sigma) of the acting head value t,
+        // final as of its two adam_one calls. It folds that value here (fold_heads_from's k = t
+        // iteration: the expression derive_weights evaluates again for w_B, on the same operands) and
+        // hands it to the feature blocks ~2 us before the block-wide fold behind the next barriers.
+        if ((ahead & 1) && t < 260) {
+            fold_heads_from(sm.ap.hp, nullptr, sm.ap.nact, PM_FOLD_TRAIN_FRESH, sm.ap.heads[0], nullptr, t, kLearn);
+            gh_publish(sp, t, gh_tag, sm.ap.heads[0][t]);
+            PM_STAMP(22);
+        }
         PM_STAMP(8); PM_STAMP_T(9, 960);
         if (!tr) {  // level-1 nodes of the scatter: 4 lanes per sampled index (duplicates recompute the
                     // same node from the same leaves: identical values)
@@ -1683,8 +1823,12 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
         if (t == 0) push_wait(sp, cs);
         __syncthreads();
     }
-    if (sp.fuse_apply) apply_finish(sp, sm.ap, cs, mode);  // unsharded: Adam ran with the gradients (phase 4)
+    // unsharded: Adam ran with the gradients (phase 4), and with it the acting heads' hand-off; an update
+    // that did not train (block-uniform) publishes them from the block-wide fold
+    if (sp.fuse_apply) apply_finish(sp, sm.ap, cs, mode, (ahead & 1) && !train, gh_tag);
     if (t == 0) {  // the counters, last: no store of theirs sits in front of a phase's vmcnt(0) wait
+        // the heads' epoch: this launch's tag is spent (every feature block read the epoch at its start)
+        if (ahead & 1) __hip_atomic_store(gh_epoch(sp), gh_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (first) {  // rollout bookkeeping (:245-249)
             c->ep_step = ep_fin;
             c->episodes = cs.episodes + ep_fin;
@@ -2520,10 +2664,13 @@ constexpr int kSideRows = 480;
 // the one-round grid: the feature blocks have the slack (r5o, same box, two interleaved passes:
 // 2 -> 1.79 / 1.81 G env-steps/s, 0 -> 1.81 / 1.77, 1 (round 4) -> 1.76 / 1.75, 3 -> 1.75 / 1.75).
 // PONGMI_SIDE_NAP: the delay in units of 1 024 clocks (default 8, ~3.4 us), bits 8.. of the argument.
-int side_sleep() {
+// With actions ahead the feature blocks store nothing while the learner loads and wait for it at their
+// end, so they start after a short nap only (kNapAhead; profiles/act_ahead_ab.txt).
+constexpr int kNapAhead = 2;
+int side_sleep(bool ahead) {
     const char* e = getenv("PONGMI_SIDE_SLEEP");
     const char* n = getenv("PONGMI_SIDE_NAP");
-    const int roles = e && *e ? atoi(e) : 2, nap = n && *n ? atoi(n) : 8;
+    const int roles = e && *e ? atoi(e) : 2, nap = n && *n ? atoi(n) : (ahead ? kNapAhead : 8);
     return (roles & 3) | (std::max(0, std::min(nap, 64)) << 8);
 }
 int device_cus() {
@@ -2572,14 +2719,37 @@ int tree_refresh_block() {
     return v;
 }
 
+unsigned learn_blocks(const pm_selfplay* sp, bool with_act, const LearnGrid& lg) {
+    unsigned blocks = 2u + (with_act ? (unsigned)lg.g.blocks() : 0u);  // learner, push-row block, side blocks
+    if (with_act && sp->featB) blocks += (unsigned)((feat_ntiles(sp->n) + lg.ftiles - 1) / lg.ftiles);
+    return blocks;
+}
+
+// Actions ahead (k_learn's `ahead` argument; pm_selfplay_act_ahead): the fused U = 1 learner launch with
+// the side blocks, whose heads are final inside the launch (the sharded step's are only after k_adam, a
+// step of U > 1 updates keeps training after it, and k_learn_multi needs the features themselves: frow).
+// The feature blocks park their tiles' accumulators in registers, two tiles per wave at most, and wait for
+// the learner, so all of them must be resident beside it: one block per CU (the launch's LDS).
+// PONGMI_ACT_AHEAD=0: the featB path from the same library (A/B; read per launch, bit-identical).
+// PONGMI_AHEAD_FORCE_TIMEOUT=1 (bit 1): test hook, the feature blocks' poll expires at once.
+int act_ahead(const pm_selfplay* sp, int mode, bool with_act, const LearnGrid& lg) {
+    if (!with_act || !sp->fuse_apply || mode != (PM_UPD_FIRST | PM_UPD_LAST) || !sp->featB || !sp->gB || !sp->gheads ||
+        sp->frow || lg.ftiles > 2 * (kLearn / 64) || (int)learn_blocks(sp, with_act, lg) > device_cus())
+        return 0;
+    const char* e = getenv("PONGMI_ACT_AHEAD");
+    if (e && *e && atoi(e) == 0) return 0;
+    const char* f = getenv("PONGMI_AHEAD_FORCE_TIMEOUT");
+    return 1 | ((f && *f && atoi(f) != 0) << 1);
+}
+
 int launch_learn(const pm_selfplay* sp, bool with_act, hipStream_t st, int mode = PM_UPD_FIRST | PM_UPD_LAST) {
     const LearnGrid lg = learn_grid(sp);
     const ActGrid& g = lg.g;
-    unsigned blocks = 2u + (with_act ? (unsigned)g.blocks() : 0u);  // learner, push-row block, side blocks
-    if (with_act && sp->featB) blocks += (unsigned)((feat_ntiles(sp->n) + lg.ftiles - 1) / lg.ftiles);
+    const unsigned blocks = learn_blocks(sp, with_act, lg);
     const int tr = tree_refresh_block();
+    const int ahead = act_ahead(sp, mode, with_act, lg);
     pm_launch(PM_TIMER_LEARN, (tr & 8) ? k_learn<true> : k_learn<false>, dim3(blocks), dim3(kLearn), st, *sp, g.chunk0,
-              g.chunk1, mode, tr, lg.ftiles, side_sleep());
+              g.chunk1, mode, tr, lg.ftiles, side_sleep(ahead & 1), ahead);
     PM_LAUNCHED("k_learn");
     return PM_OK;
 }
@@ -2628,6 +2798,11 @@ extern "C" int pm_selfplay_learn(const pm_selfplay* sp, void* stream) {
 extern "C" int pm_selfplay_learn_act(const pm_selfplay* sp, void* stream) {
     int rc = check(sp);
     return rc ? rc : launch_learn(sp, true, pm_stream(stream));
+}
+
+extern "C" int pm_selfplay_act_ahead(const pm_selfplay* sp, int32_t mode, int32_t with_act) {
+    if (check(sp)) return 0;
+    return act_ahead(sp, (int)mode, with_act != 0, learn_grid(sp)) & 1;
 }
 
 extern "C" int pm_selfplay_apply(const pm_selfplay* sp, void* stream) {

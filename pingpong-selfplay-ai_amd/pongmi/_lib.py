@@ -37,7 +37,8 @@ PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
-ABI_VERSION = 25
+ABI_VERSION = 26
+PM_GB_NONE, PM_GHEADS_LEN = 3, 264
 PM_TIMER_ACTENV, PM_TIMER_LEARN, PM_TIMER_RNN_ACT, PM_TIMER_ENV_STEP, PM_TIMER_ROLLOUT, PM_TIMER_DRQN = 0, 1, 2, 3, 4, 5
 PM_TIMER_LEARN_MULTI, PM_TIMER_N = 6, 7
 PM_ROLL_HEADS = 264
@@ -73,7 +74,8 @@ class SelfPlay(ctypes.Structure):
         [(n, c_double) for n in ("gamma", "alpha", "lr", "beta1", "beta2", "adam_eps", "min_epsilon", "epsilon_decay",
                                  "pool_ratio", "beta_start")] + \
         [("beta_frames", c_i64), ("target_update_interval", c_i64), ("seed_env", c_u64), ("seed_net", c_u64),
-         ("featB", c_void_p), ("frow", c_void_p), ("frow_ready", c_i32), ("_pad1", c_i32)]
+         ("featB", c_void_p), ("frow", c_void_p), ("frow_ready", c_i32), ("gB_ready", c_i32), ("gB", c_void_p),
+         ("gheads", c_void_p)]
 
 
 class RollReplay(ctypes.Structure):
@@ -180,6 +182,7 @@ _SIGS = {
     "pm_selfplay_learn_act": (c_i32, [c_void_p, c_void_p]),
     "pm_selfplay_actenv": (c_i32, [c_void_p, c_void_p]),
     "pm_selfplay_step_overlap": (c_i32, [c_void_p, c_void_p]),
+    "pm_selfplay_act_ahead": (c_i32, [c_void_p, c_i32, c_i32]),
     "pm_selfplay_learn_ex": (c_i32, [c_void_p, c_i32, c_i32, c_void_p]),
     "pm_selfplay_apply_ex": (c_i32, [c_void_p, c_i32, c_void_p]),
     "pm_selfplay_resample": (c_i32, [c_void_p, c_void_p]),

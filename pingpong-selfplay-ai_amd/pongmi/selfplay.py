@@ -92,7 +92,7 @@ class SelfPlayLearner:
         if self.updates_per_step < 1:
             raise ValueError("updates_per_step must be >= 1")
         self.overlap = bool(overlap)
-        self._aA_ready = False
+        self._aA = self._gB_ready = False
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise _lib.PongmiError("SelfPlayLearner runs on a ROCm device only")
@@ -143,6 +143,12 @@ class SelfPlayLearner:
         # modelB's hidden features of the next step's observations, computed with the opponents' act
         # (features are frozen: only the heads train), so the fused act + env kernel evaluates heads only
         self.featB = torch.zeros(((n + 31) // 32) * 2048, **f32) if features_ahead else None
+        # actions ahead (ABI 26): in the fused U = 1 step the learner launch's feature blocks take the next
+        # step's acting heads from the learner and store modelB's greedy action per arena (gB) instead of
+        # its features; gheads is that hand-off's granules. featB stays allocated: the fallback of a
+        # hand-off that timed out, and what every other path (act(PM_ACT_A), sharded, U > 1) writes.
+        self.gB = torch.full((n,), _lib.PM_GB_NONE, dtype=torch.int8, device=dev) if features_ahead else None
+        self.gheads = torch.zeros(_lib.PM_GHEADS_LEN, dtype=torch.int64, device=dev) if features_ahead else None
         # U > 1: ReLU(modelB's features) of every replay row's s, stored at push time, so updates 1..U-1
         # of a vector step run as one single-workgroup launch (k_learn_multi; 256 B per replay row)
         use_frow = learn_multi and self.updates_per_step > 1 and features_ahead and self.overlap and world == 1
@@ -165,6 +171,7 @@ class SelfPlayLearner:
             setattr(sp, name, ptr(getattr(self, name)))
         sp.featB = ptr(self.featB)
         sp.frow = ptr(self.frow)
+        sp.gB, sp.gheads, sp.gB_ready = ptr(self.gB), ptr(self.gheads), 0
         sp.frow_ready = int(self.frow is not None)
         sp.n, sp.n_pool, sp.batch, sp.world, sp.cap = n, self.n_pool, self.batch, self.world, self.cap
         sp.fuse_apply = int(bool(fuse_apply) and self.world == 1)
@@ -187,6 +194,25 @@ class SelfPlayLearner:
     # side-A act, or by the extra blocks of the previous step's learner launch), and sp.featB modelB's
     # features of them (computed by the same launches). Anything that changes the observations,
     # opponent ids, opponent weights or modelB's feature layers clears it.
+    # `_gB_ready` (next to it; cleared whenever `_aA_ready` is): the launch that made `_aA_ready` true was
+    # a learner launch with actions ahead (pm_selfplay_act_ahead), so sp.gB, not sp.featB, is what is
+    # current for the observations; a side-A act leaves featB current instead. It reaches the device as
+    # sp.gB_ready, set before every launch that holds a k_actenv.
+    @property
+    def _aA_ready(self):
+        return self._aA
+
+    @_aA_ready.setter
+    def _aA_ready(self, v):
+        self._aA = bool(v)
+        if not v:
+            self._gB_ready = False
+
+    def _learned_act(self, mode):
+        """After a learner launch with the next step's side-A act: who holds modelB's side of it."""
+        self._aA_ready = True
+        self._gB_ready = bool(self.lib.pm_selfplay_act_ahead(ctypes.byref(self.sp), int(mode), 1))
+
     def _frow_pushed(self, through_actenv):
         """Bookkeeping of sp.frow_ready: a push through k_env (rollout / env_step) stores no features, so
         k_learn_multi waits until those rows have left the ring (cap / n pushes through actenv)."""
@@ -207,9 +233,11 @@ class SelfPlayLearner:
         check(self.lib.pm_selfplay_act_part(ctypes.byref(self.sp), int(part), stream_ptr()), "pm_selfplay_act_part")
         if part != _lib.PM_ACT_B:
             self._aA_ready = True
+            self._gB_ready = False  # featB is current for every tile
 
     def actenv(self):
         """act(PM_ACT_B) + env_step fused into one launch (bit-identical)."""
+        self.sp.gB_ready = int(self._gB_ready)
         self._aA_ready = False
         self._frow_pushed(True)
         check(self.lib.pm_selfplay_actenv(ctypes.byref(self.sp), stream_ptr()), "pm_selfplay_actenv")
@@ -224,7 +252,7 @@ class SelfPlayLearner:
         actions (after env_step: for the observations it wrote)."""
         if act_next:
             check(self.lib.pm_selfplay_learn_act(ctypes.byref(self.sp), stream_ptr()), "pm_selfplay_learn_act")
-            self._aA_ready = True
+            self._learned_act(_lib.PM_UPD_FIRST | _lib.PM_UPD_LAST)
         else:
             check(self.lib.pm_selfplay_learn(ctypes.byref(self.sp), stream_ptr()), "pm_selfplay_learn")
 
@@ -235,7 +263,7 @@ class SelfPlayLearner:
         check(self.lib.pm_selfplay_learn_ex(ctypes.byref(self.sp), int(mode), int(bool(act_next)), stream_ptr()),
               "pm_selfplay_learn_ex")
         if act_next:
-            self._aA_ready = True
+            self._learned_act(mode)
 
     def apply_ex(self, mode):
         check(self.lib.pm_selfplay_apply_ex(ctypes.byref(self.sp), int(mode), stream_ptr()), "pm_selfplay_apply_ex")
@@ -254,9 +282,11 @@ class SelfPlayLearner:
         self._frow_pushed(True)
         if not self._aA_ready:
             self.act(_lib.PM_ACT_A)
+        self.sp.gB_ready = int(self._gB_ready)
         check(self.lib.pm_selfplay_step_sharded(ctypes.byref(self.sp), comm, self.updates_per_step, stream_ptr()),
               "pm_selfplay_step_sharded")
         self._aA_ready = True
+        self._gB_ready = False  # the sharded learner launch stores features (its heads are final after k_adam)
 
     def _step_multi(self):
         U = self.updates_per_step
@@ -264,8 +294,10 @@ class SelfPlayLearner:
             if not self._aA_ready:
                 self.act(_lib.PM_ACT_A)
             self._frow_pushed(True)
+            self.sp.gB_ready = int(self._gB_ready)
             check(self.lib.pm_selfplay_step_multi(ctypes.byref(self.sp), U, stream_ptr()), "pm_selfplay_step_multi")
             self._aA_ready = True
+            self._gB_ready = False  # update 0 of U > 1 is not the step's last: its launch stores features
             return
         sharded_vector_step(self, self.allreduce if self.world > 1 else None, U)
 
@@ -290,8 +322,9 @@ class SelfPlayLearner:
         if not self._aA_ready:
             self.act(_lib.PM_ACT_A)
         self._frow_pushed(True)
+        self.sp.gB_ready = int(self._gB_ready)
         check(self.lib.pm_selfplay_step_overlap(ctypes.byref(self.sp), stream_ptr()), "pm_selfplay_step_overlap")
-        self._aA_ready = True
+        self._learned_act(_lib.PM_UPD_FIRST | _lib.PM_UPD_LAST)
 
     # ------------------------------------------------------------------ state readout (syncs)
     def counters(self):

@@ -37,6 +37,8 @@ NAMES = {
     60: "tree blk winners + pval (t0)", 61: "tree blk level-1 sums (t0)", 62: "tree blk pushed subs (t0)",
     63: "tree blk chunk slots (t0)", 66: "learn launch: side-A act blocks end (max)",
     67: "learn launch: feature blocks end (max)",
+    22: "apply acting heads published", 68: "feature blocks: tiles done, poll begins (max)",
+    69: "feature blocks: heads in LDS (max)",
     5: "learn tree level1", 6: "learn tree level2", 20: "apply adam", 21: "apply derive", 7: "learn end",
 }
 
