@@ -799,6 +799,7 @@ def adam_step(p, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
 # Restatement of the counter-based generator libpongmi draws from (Philox4x32-10, Salmon et al.
 # SC'11), so tests can replay the device's serves / epsilon draws / PER uniforms / noise.
 TAG_SERVE, TAG_ACT, TAG_OPP, TAG_NOISE_ACT, TAG_PER, TAG_NOISE_TRAIN = 1, 2, 3, 4, 5, 6
+TAG_SEQ = 8  # the sequence sampler's draw (k_rsp_sample; restated in oracle/seqbuf.py)
 TAG_SERVE_STEP = 9
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 

@@ -181,7 +181,10 @@ __global__ __launch_bounds__(kAppend) void k_rsp_append(const pm_rnn_selfplay sp
     }
     const int total = off[kAppend];
     const int64_t base = c->seq_count;
-    for (int e = t; e < total; e += kAppend) {  // entry e: env block b with off[b] <= e < off[b + 1]
+    // deque(maxlen=seq_cap).append of `total` episodes in arena order keeps the last seq_cap of them: only
+    // those are written, so no two threads share a table slot (entries e and e + seq_cap of one step would)
+    const int skip = total > sp.seq_cap ? total - (int)sp.seq_cap : 0;
+    for (int e = skip + t; e < total; e += kAppend) {  // entry e: env block b with off[b] <= e < off[b + 1]
         int lo = 0, hi = kAppend;
         while (hi - lo > 1) {
             const int mid = (lo + hi) >> 1;

@@ -11,7 +11,11 @@
 2. the sequence buffer: every stored episode is one contiguous trajectory of >= T steps ending in
    done, the latest memory_size are kept, sampled sequences are windows of stored episodes, the
    update runs exactly when len(memory) > batch * min_episodes_for_training_start, epsilon decays
-   once per finished episode;
+   once per finished episode (structural checks; WHICH episodes the table holds, in which order,
+   which window the sampler draws and that act / rew / next / done belong to it are pinned exactly,
+   step by step, to the host model of the reference's deque in tests/test_gpu_rnn_seqbuf.py — down
+   to a capacity below one step's storable episodes, where k_rsp_append used to let two threads
+   write one table slot and now writes only the step's newest seq_cap entries);
 3. determinism, and two data-parallel ranks (gradient sum + contributing-rank count) stay identical.
 
 The `_ragged` tests repeat 1, 2 and the overlapped / split-tile identities at arena counts that are
