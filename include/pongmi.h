@@ -362,6 +362,9 @@ typedef struct pm_drqn {
     int32_t reserved;
 } pm_drqn;
 
+/* Bytes of workspace for (batch, T), or -1 for exactly the sizes every other pm_drqn_* entry point
+ * rejects: batch not a multiple of 32 in [32, 256], or T outside [1, 64]. Size the allocation from it
+ * and treat -1 as an error before allocating anything. */
 int64_t pm_drqn_work_bytes(int32_t batch, int32_t T);
 /* Zero-fill d->work (pm_drqn_work_bytes(d->batch, d->T) bytes) on the stream (ABI 20): call once after
  * allocating the workspace, before the first pm_drqn_grads / pm_drqn_update on it. */

@@ -1169,7 +1169,7 @@ extern "C" int pm_diag_clear_drqn(void) {
 #endif
 
 extern "C" int64_t pm_drqn_work_bytes(int32_t batch, int32_t T) {
-    if (batch < 32 || batch % 32 || T < 1) return -1;
+    if (batch < 32 || batch > 256 || batch % 32 || T < 1 || T > 64) return -1;  // the sizes check() rejects
     return dq_layout(batch, T, nullptr, nullptr);
 }
 

@@ -31,15 +31,16 @@ class DRQNLearner:
         target None = a copy of modelB (targetB.load_state_dict(modelB.state_dict()), :336-338)."""
         self.lib = _lib.load()
         self.device = torch.device(device)
+        self.batch, self.T = int(batch), int(T)
+        # -1 for exactly the sizes pm_drqn_init would reject: raise before anything is allocated
+        nbytes = self.lib.pm_drqn_work_bytes(self.batch, self.T)
+        if nbytes < 0:
+            raise ValueError(f"DRQNLearner: batch {self.batch} (multiple of 32 in [32, 256]) / T {self.T} (1..64)")
         self.params = self._block(modelB)
         self.target = self._block(target) if target is not None else self.params.clone()
         self.adam_m = torch.zeros(PM_RNN_NPARAM, dtype=torch.float32, device=self.device)
         self.adam_v = torch.zeros(PM_RNN_NPARAM, dtype=torch.float32, device=self.device)
         self.grad = torch.zeros(PM_RNN_NPARAM + 4, dtype=torch.float32, device=self.device)
-        self.batch, self.T = int(batch), int(T)
-        nbytes = self.lib.pm_drqn_work_bytes(self.batch, self.T)
-        if nbytes < 0:
-            raise ValueError("invalid batch / T")
         # zero-filled before first use (pm_drqn_init below): the hand-off slots' tags and the tag epoch
         # (flags[0]) must not start as whatever the allocator hands back
         self.work = torch.empty((nbytes + 15) // 16 * 4, dtype=torch.float32, device=self.device)

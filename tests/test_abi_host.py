@@ -58,6 +58,25 @@ def test_entry_points_reject_bad_arguments_without_a_gpu():
     assert L.pm_env_reset(None, None, None, None, 0, 0, None, None, None, 0, None) == 0  # n = 0 is a no-op
 
 
+def test_drqn_work_bytes_rejects_exactly_what_check_rejects():
+    """pm_drqn_work_bytes is -1 for every (batch, T) the pm_drqn_* entry points reject (batch not a
+    multiple of 32 in [32, 256], T outside [1, 64]), so a caller sizing its allocation from it fails
+    before allocating; every accepted size is positive and grows with batch and T. The largest,
+    (256, 64), is the sum of the workspace's pieces: 4256 floats per (step, sequence) column plus the
+    per-sequence and fixed pieces (pm_drqn.hip, dq_layout)."""
+    from pongmi import _lib
+    L = _lib.load()
+    for b, t in ((0, 8), (16, 8), (48, 8), (288, 8), (1 << 20, 8), (-32, 8), (64, 0), (64, 65), (64, -1), (256, 1 << 20)):
+        assert L.pm_drqn_work_bytes(b, t) == -1, (b, t)
+    sizes = {(b, t): L.pm_drqn_work_bytes(b, t) for b in range(32, 257, 32) for t in (1, 2, 64)}
+    for (b, t), n in sizes.items():
+        assert n > 4 * 4256 * b * t, (b, t, n)
+        assert t == 1 or n > sizes[b, 1 if t == 2 else 2], (b, t, n)
+        assert b == 32 or n > sizes[b - 32, t], (b, t, n)
+    assert L.pm_drqn_work_bytes(256, 64) == 4 * (4256 * 16384 + (8 + 3 * 128 + 8) * 256 + 2 * 128 * 132 + 2 * 704 +
+                                                 2 * 256 + 2 * 256 + 64 + 64)
+
+
 def test_env_params_derived_constants_use_python_expressions():
     from pongmi.env import env_params
     p = env_params(ball_mass=1.3, world_ball_radius=0.031, paddle_width=0.21, speed_increment=0.1)

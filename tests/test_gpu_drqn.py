@@ -355,3 +355,231 @@ def test_drqn_timeout_voids_update(golden):
     R = DRQNLearner(_sd(gr), batch=64, T=8, target_update_interval=1)
     R.update(*b)
     assert torch.equal(L.params, R.params) and torch.equal(L.adam_v, R.adam_v) and torch.equal(L.target, R.target)
+
+
+# ------------------------------------------------------------------ every size the ABI accepts
+def _np_sd(golden):
+    return {k[7:]: v for k, v in golden("rnn").items() if k.startswith("params.")}
+
+
+def _perturbed(sd, rng):
+    """A target net that differs from modelB in every parameter (epsilon buffers kept)."""
+    return {k: (v + rng.normal(0, 0.02, v.shape).astype(np.float32)) if "epsilon" not in k else v for k, v in sd.items()}
+
+
+def _rand_batch(rng, B, T, rewards=(-1, 0, 1)):
+    obs = rng.uniform(0, 1, (B, T, 7)).astype(np.float32)
+    nxt = rng.uniform(0, 1, (B, T, 7)).astype(np.float32)
+    act = rng.integers(0, 3, (B, T)).astype(np.int64)
+    rew = rng.choice(np.array(rewards, np.float32), (B, T)).astype(np.float32)
+    done = rng.random((B, T)) < 0.3
+    return obs, act, rew, nxt, done
+
+
+def _tt(x):
+    return {k: torch.from_numpy(v) for k, v in x.items()} if isinstance(x, dict) else tuple(torch.from_numpy(v) for v in x)
+
+
+def _check_update(L, orc, tsd, batch, at, what):
+    """One grads() + apply() of L on `batch` from L's own current parameters: loss vs the float64
+    oracle (rtol 1e-4), gradients at the file's conditioned bar, clip + Adam bit for bit, status 0.
+    Returns error / bar."""
+    sd64, tsd64 = _f64(L.state_dict()), _f64(tsd)
+    L.grads(*_tt(batch))
+    info = orc.drqn_grads(sd64, tsd64, *batch)
+    np.testing.assert_allclose(L.stats()["loss"], info["loss"], rtol=1e-4, err_msg=what)
+    p0, m0, v0 = _snap(L)
+    L.apply()  # forms the sigma gradients
+    w, _ = _assert_grads_conditioned(_grads(L), orc, sd64, tsd64, batch, what)
+    _assert_apply_exact(L, p0, m0, v0, at, what)
+    assert L.stats()["status"] == 0, what
+    return w
+
+
+# (B, 3): every batch size (nct = B/32 sizes k_dq_embed's grid and k_dq_wgrad's K loops, 5B/2 k_dq_recur's
+# grid); T = 2: the first use of step 0's prefetch of step 1; T = 9: the second trip of the 8-strided
+# write-out of H, for kg == 0 only; T = 22 / 23: the last sequence whose gate scratch is in LDS (kGcLds)
+# and the first whose scratch is in global memory, at one tile (32), an odd tile count (96) and the
+# largest batch; (256, 64): the largest workspace (C0 = 16384 columns, ~300 MB)
+SWEEP = ([(B, 3) for B in (128, 160, 192, 224)] + [(32, T) for T in (2, 9, 22, 23)] +
+         [(96, T) for T in (2, 9, 22, 23, 64)] + [(224, 9), (256, 22), (256, 23), (256, 64)])
+
+
+@pytest.mark.parametrize("B,T", SWEEP)
+def test_drqn_size_sweep(golden, orc, B, T):
+    """Every batch size and every sequence-length edge the ABI accepts, against the oracle: the split
+    path's loss, gradients, clip + Adam and status; the fused update() of a second learner bit for bit
+    (params, both moments, gradient, norm); then a second update of the same learner on a new batch
+    from the parameters the first left: the workspace reused with a new tag epoch, H[., 0] and the
+    zero rows of XT as the first update left them."""
+    from pongmi.drqn import DRQNLearner
+    sd = _np_sd(golden)
+    rng = np.random.default_rng(B * 100 + T)
+    tsd = _perturbed(sd, rng)
+    batch = _rand_batch(rng, B, T)
+    L = DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T)
+    w0 = _check_update(L, orc, tsd, batch, 1, f"B={B} T={T}")
+    R = DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T)
+    R.update(*_tt(batch))
+    assert R.stats()["status"] == 0
+    stL, stR = L.stats(), R.stats()
+    assert stL["norm"] == stR["norm"] and stL["loss"] == stR["loss"]
+    for name in ("params", "adam_m", "adam_v", "grad"):
+        assert torch.equal(getattr(L, name), getattr(R, name)), f"fused vs split {name}, B={B} T={T}"
+    del R
+    # the second batches' seed offset is chosen on the CPU, from the oracle and the reference's float32
+    # autograd alone, so that no shape's bar widens: with 50000, (160, 3)'s batch puts one shared-head
+    # pre-activation at -7e-8, whose ReLU float32 and float64 decide differently (the reference's own
+    # gradient is then 1e-2 x max|g| from float64, and so is the device's); with 90000 the reference is
+    # within 1.5e-5 x max|g| of float64 at every shape
+    batch2 = _rand_batch(np.random.default_rng(90000 + B * 100 + T), B, T)
+    w1 = _check_update(L, orc, tsd, batch2, 2, f"B={B} T={T} second update")
+    assert L.stats()["steps"] == 2
+    print(f"B={B} T={T}: error / bar {max(w0, w1):.4f}")
+
+
+# ------------------------------------------------------------------ constructed batches
+CONSTRUCTED = [(32, 2), (32, 23)]  # one shape per gate-scratch path (LDS, global)
+# seeds per T, chosen on the CPU so that the oracle alone meets each test's precondition (asserted there)
+HUBER_SEED = {2: 0, 23: 0}
+TIE_SEED = {2: 0, 23: 0}
+
+
+def _huber_case(golden, T):
+    sd = _np_sd(golden)
+    rng = np.random.default_rng(HUBER_SEED[T])
+    tsd = _perturbed(sd, rng)
+    return sd, tsd, _rand_batch(rng, 32, T, rewards=(-3, -0.2, 0.2, 3))
+
+
+@pytest.mark.parametrize("B,T", CONSTRUCTED)
+def test_drqn_both_huber_branches(golden, orc, B, T):
+    """Rewards from {-3, -0.2, 0.2, 3}: by the oracle's own q and y at least 4 sequences sit on the
+    quadratic side of smooth-L1 (|d| < 1), at least 4 on the linear side, and none within 1e-3 of the
+    switch (where float32 and float64 could disagree on the branch)."""
+    from pongmi.drqn import DRQNLearner
+    sd, tsd, batch = _huber_case(golden, T)
+    info = orc.drqn_grads(_f64(sd), _f64(tsd), *batch)
+    ad = np.abs(info["q"] - info["y"])
+    assert (ad < 1).sum() >= 4 and (ad > 1).sum() >= 4 and not (np.abs(ad - 1) < 1e-3).any(), ad
+    _check_update(DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T), orc, tsd, batch, 1, f"huber T={T}")
+
+
+@pytest.mark.parametrize("B,T", CONSTRUCTED)
+def test_drqn_done_all_ones_all_zeros(golden, orc, B, T):
+    """done at the last step all ones, then all zeros. With all ones the target term is multiplied by
+    exactly 0, so the gradient and the loss do not depend on gamma, bit for bit."""
+    from pongmi._lib import PM_RNN_NPARAM
+    from pongmi.drqn import DRQNLearner
+    sd = _np_sd(golden)
+    rng = np.random.default_rng(7000 + T)
+    tsd = _perturbed(sd, rng)
+    obs, act, rew, nxt, done = _rand_batch(rng, B, T)
+    outs = []
+    for last in (True, False):
+        done = done.copy()
+        done[:, -1] = last
+        batch = (obs, act, rew, nxt, done)
+        L = DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T)
+        _check_update(L, orc, tsd, batch, 1, f"done all {int(last)} T={T}")
+        outs.append((L.grad.clone(), L.stats()["loss"]))
+        if last:
+            H = DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T, gamma=0.5)
+            H.update(*_tt(batch))
+            assert H.stats()["status"] == 0
+            assert torch.equal(H.grad[:PM_RNN_NPARAM], L.grad[:PM_RNN_NPARAM]) and H.stats()["loss"] == outs[0][1]
+    assert not torch.equal(outs[0][0], outs[1][0])  # the target term does count when done is 0
+
+
+@pytest.mark.parametrize("B,T", CONSTRUCTED)
+def test_drqn_reads_act_rew_done_at_last_step_only(golden, orc, B, T):
+    """act, rew and done at steps 0 .. T-2 replaced by other valid values (actions permuted within
+    {0, 1, 2}, rewards x 7, done flipped): the gradient, the loss and mean Q are bit-identical, as in
+    the reference, which reads only [:, -1]."""
+    from pongmi._lib import PM_RNN_NPARAM
+    from pongmi.drqn import DRQNLearner
+    sd = _np_sd(golden)
+    rng = np.random.default_rng(8000 + T)
+    tsd = _perturbed(sd, rng)
+    obs, act, rew, nxt, done = _rand_batch(rng, B, T)
+    act2, rew2, done2 = act.copy(), rew.copy(), done.copy()
+    act2[:, :-1] = (act[:, :-1] + 1) % 3
+    rew2[:, :-1] = rew[:, :-1] * 7
+    done2[:, :-1] = ~done[:, :-1]
+    assert (act2[:, :-1] != act[:, :-1]).all() and (done2[:, :-1] != done[:, :-1]).all() and (rew2 != rew).any()
+    outs = []
+    for b in ((obs, act, rew, nxt, done), (obs, act2, rew2, nxt, done2)):
+        L = DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T)
+        L.grads(*_tt(b))
+        st = L.stats()
+        assert st["status"] == 0
+        outs.append((L.grad[:PM_RNN_NPARAM].clone(), st["loss"], st["q_mean"]))
+    np.testing.assert_allclose(outs[0][1], orc.drqn_grads(_f64(sd), _f64(tsd), obs, act, rew, nxt, done)["loss"], rtol=1e-4)
+    assert torch.equal(outs[0][0], outs[1][0]) and outs[0][1:] == outs[1][1:]
+
+
+def _tie_case(golden, T):
+    """modelB with fc_A rows 0 and 1 identical (weight and bias; mu, sigma and epsilon), so
+    Q_B[0] == Q_B[1] exactly for every input; the target's rows stay distinct. Both get the fixture's
+    row 2, the action its parameters favour, and row 2 gets the old row 0, so that the tie is the
+    maximum on most sequences."""
+    sd = {k: v.copy() for k, v in _np_sd(golden).items()}
+    rng = np.random.default_rng(TIE_SEED[T])
+    tsd = _perturbed(sd, rng)
+    for k in sd:
+        if k.startswith("fc_A."):
+            sd[k][[0, 1, 2]] = sd[k][[2, 2, 0]]
+    return sd, tsd, _rand_batch(rng, 32, T)
+
+
+def _tie_precondition(orc, sd, tsd, batch):
+    """From the oracle alone: a* is never 1, at least a quarter of the sequences have
+    Q_B(next)[0] == Q_B(next)[1] > Q_B(next)[2], and taking the last maximum on those (a* = 1) would
+    move the loss by more than 10 x the test's rtol of 1e-4."""
+    obs, act, rew, nxt, done = batch
+    B = obs.shape[0]
+    z = np.zeros((B, 128))
+    qn = orc.rnn_forward(orc.rnn_effective(_f64(sd), True), nxt, z, z)[0]
+    qt = orc.rnn_forward(orc.rnn_effective(_f64(tsd), False), nxt, z, z)[0]
+    a = orc.argmax_first(qn)
+    tie = (qn[:, 0] == qn[:, 1]) & (qn[:, 0] > qn[:, 2])
+    assert not (a == 1).any() and tie.sum() * 4 >= B, (a, tie)
+    info = orc.drqn_grads(_f64(sd), _f64(tsd), *batch)
+    y1 = rew[:, -1].astype(np.float64) + 0.99 * qt[np.arange(B), np.where(tie, 1, a)] * (~done[:, -1])
+    d = np.abs(info["q"] - y1)
+    loss1 = np.mean(np.where(d < 1, 0.5 * d * d, d - 0.5))
+    assert abs(loss1 - info["loss"]) > 1e-3 * info["loss"], (loss1, info["loss"])
+    return int(tie.sum())
+
+
+@pytest.mark.parametrize("B,T", CONSTRUCTED)
+def test_drqn_argmax_exact_ties_take_first_index(golden, orc, B, T):
+    """The double-DQN argmax on an exact tie takes the first maximum, as torch's argmax and the
+    oracle do: a kernel that took the last, or that summed actions 0 and 1 in different orders, would
+    pick another target Q and miss the loss."""
+    from pongmi.drqn import DRQNLearner
+    sd, tsd, batch = _tie_case(golden, T)
+    n = _tie_precondition(orc, sd, tsd, batch)
+    print(f"ties T={T}: {n} of {B} sequences with Q_B(next)[0] == Q_B(next)[1] > Q_B(next)[2]")
+    _check_update(DRQNLearner(_tt(sd), _tt(tsd), batch=B, T=T), orc, tsd, batch, 1, f"ties T={T}")
+
+
+# ------------------------------------------------------------------ arguments
+@pytest.mark.parametrize("kw", [dict(batch=b) for b in (0, 16, 48, 288, 1 << 20)] + [dict(T=t) for t in (0, 65)])
+def test_drqn_rejects_bad_sizes_before_allocating(golden, kw):
+    """Sizes pm_drqn_init rejects raise from the constructor before it allocates anything on the
+    device (pm_drqn_work_bytes returns -1 for them, and the constructor asks it first), so no kernel
+    is launched and no buffer exists to compare; a learner built afterwards works."""
+    from pongmi import _lib
+    from pongmi.drqn import DRQNLearner
+    gr, gd = golden("rnn"), golden("drqn")
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    with pytest.raises((ValueError, _lib.PongmiError)):
+        DRQNLearner(_sd(gr), **kw)
+    assert torch.cuda.max_memory_allocated() - base == 0 and torch.cuda.memory_allocated() == base
+    L = DRQNLearner(_sd(gr), batch=64, T=8)
+    L.update(*(torch.from_numpy(x) for x in _batch(gd, 0)))
+    assert L.stats()["status"] == 0 and L.stats()["steps"] == 1
+    np.testing.assert_allclose(L.stats()["loss"], gd["u0_loss"], rtol=1e-4)
