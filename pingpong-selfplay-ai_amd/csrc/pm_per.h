@@ -249,25 +249,40 @@ __device__ __forceinline__ int per_group_find(const double (&v)[NV], double x, d
     for (int e = 0; e < NV; ++e) acc += v[e];
     const double s0 = quad_f64<0>(acc), s1 = quad_f64<1>(acc), s2 = quad_f64<2>(acc);
     const double ex = q == 0 ? 0.0 : (q == 1 ? s0 : (q == 2 ? s0 + s1 : (s0 + s1) + s2));
-    int hit = -1, nz = -1;
-    double hb = 0.0, hv = 0.0, nb = 0.0, nv = 0.0, run = ex;
+    // Compare-and-select code, no branch per value. pre[e]: the running sum in front of v[e] (the same
+    // additions in the same order). The first hit is found walking down from the last value, so the
+    // earliest one is left standing; the last nonzero value is only looked for when the group has no
+    // hit (rounding left x at or past the group's total).
+    double pre[NV + 1];
+    pre[0] = ex;
 #pragma unroll
-    for (int e = 0; e < NV; ++e) {
-        if (hit < 0 && run + v[e] > x) { hit = e; hb = run; hv = v[e]; }
-        if (v[e] > 0.0) { nz = e; nb = run; nv = v[e]; }
-        run += v[e];
+    for (int e = 0; e < NV; ++e) pre[e + 1] = pre[e] + v[e];
+    int k = -1;
+    double hb = 0.0, hv = 0.0;
+#pragma unroll
+    for (int e = NV - 1; e >= 0; --e) {
+        const bool h = pre[e + 1] > x;
+        k = h ? e : k;
+        hb = h ? pre[e] : hb;
+        hv = h ? v[e] : hv;
     }
-    const unsigned gh = (unsigned)(__ballot(hit >= 0) >> g0) & 15u;
-    const unsigned gn = (unsigned)(__ballot(nz >= 0) >> g0) & 15u;
-    int src, k;
+    const unsigned gh = (unsigned)(__ballot(k >= 0) >> g0) & 15u;
+    int src;
     if (gh) {
         src = __ffs(gh) - 1;
-        k = hit;
-    } else {
+    } else {  // group-uniform
+        hb = ex;
+        hv = 0.0;
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            const bool z = v[e] > 0.0;
+            k = z ? e : k;
+            hb = z ? pre[e] : hb;
+            hv = z ? v[e] : hv;
+        }
+        const unsigned gn = (unsigned)(__ballot(k >= 0) >> g0) & 15u;
         src = gn ? 31 - __clz(gn) : 0;
-        k = nz < 0 ? 0 : nz;
-        hb = nz < 0 ? ex : nb;
-        hv = nz < 0 ? 0.0 : nv;
+        k = k < 0 ? 0 : k;
     }
     // every lane computed its candidate; take lane src's (the branch above is group-uniform)
     const int kk = quad_sel_i32(k, src);
@@ -286,7 +301,13 @@ struct NoHook {
 };
 // l2done(): called by every thread once the level-2 search is done (before the level-1 loads), where
 // a caller issues work whose loads must not delay the chunk-sum round trip.
-template <class UFn, class OutFn, class Hook = NoHook>
+// RAW: out(j, idx, pa, total) instead, the leaf and the total the weight is formed from: the fp64 pow
+// (~300 instructions and two divisions) then no longer stands between the leaf search and whatever
+// the caller does with idx. The caller evaluates per_is_weight(size, pa, total, beta) itself.
+__device__ __forceinline__ float per_is_weight(int64_t size, double pa, double total, double beta) {
+    return (float)pow((double)size * (pa / total), -beta);
+}
+template <bool RAW = false, class UFn, class OutFn, class Hook = NoHook>
 __device__ inline void per_sample_block(bool active, int64_t size, const PerTree& tr, const PushRange& pr, double beta,
                                         int j0, int bs, PerSampleSmem& sm, UFn ufn, OutFn out, Hook l2done = Hook()) {
     const int t = threadIdx.x, q = t & 3;
@@ -376,18 +397,29 @@ __device__ inline void per_sample_block(bool active, int64_t size, const PerTree
 #pragma unroll
             for (int k = 0; k < 16; ++k) f[k] = lo + k < pr.cap ? tr.leaf[lo + k] : 0.f;
         }
+        // covers(lo + k) and lo + k < size as ranges of k, one set per lane, instead of a ring distance
+        // and a 64-bit compare per leaf: leaf k lies d0 + k into the ring from pos while k < kw (the
+        // ring's wrap), k - kw after it, and is in the push range when that is below n.
         const int64_t d0 = pr.dist(lo);
+        const int64_t wrap = pr.cap - d0;
+        const int kw = (int)(wrap < 0 ? 0 : (wrap < 16 ? wrap : 16));
+        const int ka = min(kw, (int)(pr.n - d0 < 0 ? 0 : (pr.n - d0 < 16 ? pr.n - d0 : 16)));
+        const int kb = (int)(wrap + pr.n < 0 ? 0 : (wrap + pr.n < 16 ? wrap + pr.n : 16));
+        const int ks = (int)(size - lo < 0 ? 0 : (size - lo < 16 ? size - lo : 16));
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            int64_t d = d0 + k;
-            if (d >= pr.cap) d -= pr.cap;
-            lv[k] = lo + k < size ? (double)(d < pr.n ? pr.pval : f[k]) : 0.0;
+            const bool cov = k < ka || (k >= kw && k < kb);
+            const double lf = (double)(cov ? pr.pval : f[k]);
+            lv[k] = k < ks ? lf : 0.0;
         }
     }
     double b0, pa;
     const int k = per_group_find<16>(lv, x - before - b1, b0, pa);
     PM_BLK(6);
-    if (q == 0 && j < bs) out(j, sb * PER_SUB + k, (float)pow((double)size * (pa / total), -beta));
+    if (q == 0 && j < bs) {
+        if constexpr (RAW) out(j, sb * PER_SUB + k, pa, total);
+        else out(j, sb * PER_SUB + k, per_is_weight(size, pa, total, beta));
+    }
     PM_BLK(7);
 }
 

@@ -95,12 +95,7 @@ __device__ __forceinline__ PushRange push_of(const pm_selfplay& sp, int64_t pos,
 // push has not landed yet (update 0, drawn beside k_env: the tree accounts for it and its leaves read
 // as the pushed value); otherwise (updates 1..U-1) the replay is as k_env left it. The fill is the
 // post-push one either way: pos/size advance only when the step commits.
-// NS: samples per block (PER_BS, or 32 for the split forward of k_actenv's sampler blocks: lanes of the
-// block's upper half then descend for samples no output is taken from).
-template <int NS = PER_BS, class Hook = NoHook>
-__device__ __forceinline__ void sample_block(const pm_selfplay& sp, int b, bool pending, PerSampleSmem& sm,
-                                             int64_t* sidx = nullptr, Hook l2done = Hook()) {
-    static_assert(NS == PER_BS || NS == PER_BS / 2, "64 or 32 samples per block");
+__device__ __forceinline__ void sample_block(const pm_selfplay& sp, int b, bool pending, PerSampleSmem& sm) {
     const pm_ctrl* c = sp.ctrl;
     const int64_t s = c->size + sp.n;
     const int64_t size = s < sp.cap ? s : sp.cap;
@@ -108,8 +103,8 @@ __device__ __forceinline__ void sample_block(const pm_selfplay& sp, int b, bool 
     const PushRange pr = pending ? push_of(sp, c->pos, c->size, c->max_prio) : PushRange{0, 0, sp.cap, 0.f};
     const uint64_t key = sp.seed_env;
     per_sample_block(
-        size >= sp.batch, size, per_tree(sp.per_work, sp.cap), pr, beta_of(sp, frame), b * NS,
-        min(sp.batch, b * NS + NS), sm,
+        size >= sp.batch, size, per_tree(sp.per_work, sp.cap), pr, beta_of(sp, frame), b * PER_BS,
+        min(sp.batch, b * PER_BS + PER_BS), sm,
         [&](int j) {
             const U4 r = philox64((uint32_t)j, TAG_PER, (uint64_t)frame, key);
             return u53(r.x, r.y);
@@ -117,9 +112,7 @@ __device__ __forceinline__ void sample_block(const pm_selfplay& sp, int b, bool 
         [&](int j, int64_t idx, float w) {
             sp.idx[j] = idx;
             sp.isw[j] = w;
-            if (sidx) sidx[j - b * NS] = idx;
-        },
-        l2done);
+        });
 }
 
 // Both players act (train_iterative.py:240-241) on the matrix cores: ActGrid blocks, modelB tiles
@@ -347,14 +340,47 @@ struct SampleFwd32Smem {
 };
 __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b, SampleFwd32Smem& sm) {
     constexpr int NS = PER_BS / 2;
+    // The control block is read once, here, in the chunk sums' round trip (sample_block's fields, with
+    // the pending push): `active`, the push range of `mine` and beta all come from these values. A
+    // second read after the descent is a dependent round trip in front of the row loads. pm_ctrl is
+    // written by the learner launches (k_learn / k_adam: apply_finish and max_prio; k_commit;
+    // k_learn_multi) and k_tree_repaired; the stream orders every one of them before or after this
+    // launch, none runs beside it.
+    const pm_ctrl* c = sp.ctrl;
+    const int64_t csize = c->size, cpos = c->pos, cframe = c->frame_idx;
+    const float cmaxp = c->max_prio;
+    const int64_t s = csize + sp.n;
+    const int64_t size = s < sp.cap ? s : sp.cap;
+    const int64_t frame = cframe + 1;  // frame_idx += 1 before sampling (:136)
+    const bool active = size >= sp.batch;  // learner_active(sp)
+    const PushRange pr = push_of(sp, cpos, csize, cmaxp);
+    const double beta = beta_of(sp, frame);
+    const uint64_t key = sp.seed_env;
+    // this lane's sample (q == 0 lanes of waves 0-1) as the descent leaves it: the leaf and the total
+    // of its IS weight, which is formed behind the row loads below (only k_learn reads isw)
+    int wj = -1;
+    double wpa = 0.0, wtot = 1.0;
     // the forward's weights are staged once the top level of the descent is done: LDS DMA in flight
     // makes hipcc wait vmcnt(0) at the next use of a plain load, which would put the 20 KB staging in
     // front of the chunk-sum round trip
-    sample_block<NS>(sp, b, true, sm.per, sm.sidx, [&] {
-        stage_frags_lds(sp.w_B, sm.lw, b * 5);
-        copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
-    });
-    if (!learner_active(sp)) return;  // block-uniform
+    per_sample_block<true>(
+        active, size, per_tree(sp.per_work, sp.cap), pr, beta, b * NS, min(sp.batch, b * NS + NS), sm.per,
+        [&](int j) {
+            const U4 r = philox64((uint32_t)j, TAG_PER, (uint64_t)frame, key);
+            return u53(r.x, r.y);
+        },
+        [&](int j, int64_t idx, double pa, double total) {
+            sp.idx[j] = idx;
+            sm.sidx[j - b * NS] = idx;
+            wj = j;
+            wpa = pa;
+            wtot = total;
+        },
+        [&] {
+            stage_frags_lds(sp.w_B, sm.lw, b * 5);
+            copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
+        });
+    if (!active) return;  // block-uniform
     __syncthreads();  // sidx, staged weights
     PM_BLK(1);
     const int lane = threadIdx.x & 63, B = sp.batch;
@@ -363,19 +389,24 @@ __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b,
     const int jt = wv & 1;
     const int j = b * NS + (lane & 31);
     const int64_t id = sm.sidx[min(j, B - 1) - b * NS];
-    const pm_ctrl* c = sp.ctrl;
-    const bool mine = j < B && !push_of(sp, c->pos, c->size, c->max_prio).covers(id);
+    const bool mine = j < B && !pr.covers(id);
+    // The row's six loads (4 layer-1 inputs, reward, action|done bits), then the weight. In this order
+    // hipcc issues the six back to back (no vmcnt wait among them; with the pow in front of them it
+    // reused the first load's register and waited for it before the other four) and starts the
+    // weight's fp64 code after the last: plain source order, no fence and no select needed (a select
+    // for tile_inputs' conditional o[0] plus a scheduling fence measured the same).
+    const int h = lane >> 5;
     float xs[4];
     const float* tr = sp.trans + id * PM_TRANS_F;
-    tile_inputs(tr + (nxt ? 8 : 0), lane >> 5, xs);
+    tile_inputs(tr + (nxt ? 8 : 0), h, xs);
     const float rb0 = tr[7], rb1 = tr[15];
+    if (wj >= 0) sp.isw[wj] = per_is_weight(size, wpa, wtot, beta);
     f32x16 c2;
     hidden_half(sm.lw, xs, lane, jt, c2);
     const float* hf0 = sm.hf;
     const float* hf1 = sm.hf + 264;
     float ab[4] = {0.f, 0.f, 0.f, 0.f}, at[4] = {0.f, 0.f, 0.f, 0.f};
     float* row = sp.hfeat + (size_t)j * 80;
-    const int h = lane >> 5;
     if (jt == 0) {
         heads_half(hf0, c2, lane, 0, ab);
         if (nxt) heads_half(hf1, c2, lane, 0, at);
@@ -456,8 +487,11 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
         if (threadIdx.x < 65)
             reinterpret_cast<float4*>(lw + F_H)[threadIdx.x] =
                 reinterpret_cast<const float4*>(sp.w_B + PLAIN + F_H)[threadIdx.x];
+        // featB holds feat_ntiles(n) tiles: in a ragged last block the waves past n take the last tile
+        // again (their rows are stored nowhere) instead of reading up to 6 tiles past its end
+        const int tlast = feat_ntiles(sp.n) - 1;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) feat_load(sp.featB, blk * 8 + 2 * wv + k, lane, fc2[k]);
+        for (int k = 0; k < 2; ++k) feat_load(sp.featB, min(blk * 8 + 2 * wv + k, tlast), lane, fc2[k]);
     } else if (ACT) {
         stage_frags_lds(sp.w_B, lw, blk);
 #pragma unroll

@@ -12,7 +12,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ["PONGMI_LIB"] = os.path.join(ROOT, "pingpong-selfplay-ai_amd", "pongmi", "libpongmi_diag.so")
+os.environ["PONGMI_LIB"] = os.environ.get("PONGMI_DIAG_LIB") or os.path.join(  # another diagnostic build
+    ROOT, "pingpong-selfplay-ai_amd", "pongmi", "libpongmi_diag.so")
 sys.path.insert(0, os.path.join(ROOT, "pingpong-selfplay-ai_amd"))
 sys.path.insert(0, ROOT)
 
@@ -80,7 +81,7 @@ def main():
         q = lambda v: " ".join(f"{x:6.2f}" for x in np.percentile(v, [0, 50, 90, 100]))  # noqa: E731
         print(f"k_actenv sampler+forward blocks ({nsb}), times from the first env block's begin (min p50 p90 max):")
         print(f"  begin {q(s[:, 0])} | level2 {q(s[:, 4])} | level1 {q(s[:, 5])} | leaves {q(s[:, 6])} | "
-              f"sampled {q(s[:, 1])} | end {q(s[:, 2])}")
+              f"idx out {q(s[:, 7])} | sampled {q(s[:, 1])} | end {q(s[:, 2])}")
 
 
 if __name__ == "__main__":
