@@ -609,8 +609,9 @@ def _wave_incl_scan(v):
     return v
 
 
-def _round_prefix(vals):
-    """per_round_prefix for one round from base 0: vals [1024] chunk sums -> (incl [1024], total)."""
+def _round_prefix(vals, base=0.0):
+    """per_round_prefix for one round on top of `base` (the running total of the earlier rounds):
+    vals [1024] chunk sums -> (incl [1024], the running total after the round)."""
     v = vals.reshape(256, 4)
     run = np.cumsum(v, axis=1)  # sequential per thread (4 terms: cumsum is left to right)
     acc = run[:, 3]
@@ -620,18 +621,30 @@ def _round_prefix(vals):
         sc = _wave_incl_scan(acc[64 * wv:64 * wv + 64])
         wsum.append(sc[63])
         excl = np.concatenate([[0.0], sc[:-1]])
-        wb = 0.0
+        wb = base
         for k in range(wv):
             wb = wb + wsum[k]
         ex = wb + excl
         incl[256 * wv:256 * wv + 256] = (ex[:, None] + run[64 * wv:64 * wv + 64]).ravel()
-    total = (((0.0 + wsum[0]) + wsum[1]) + wsum[2]) + wsum[3]
+    total = (((base + wsum[0]) + wsum[1]) + wsum[2]) + wsum[3]
     return incl, total
+
+
+def _bsearch(flags, lo, hi):
+    """The device's binary searches (per_lds_search; the fallback's search for the round's last
+    nonzero chunk) with their own midpoints: the first True of flags in [lo, hi), hi if none is met."""
+    while lo < hi:
+        mid = (lo + hi) >> 1
+        if flags[mid]:
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
 
 
 def _group_find(v, x):
     """per_group_find: 4 lanes x NV values in order; first value whose running sum exceeds x, else the
-    last nonzero one. Returns (index, sum before it, value)."""
+    last nonzero one. Returns (index, sum before it, value, whether the fallback decided)."""
     nv = len(v) // 4
     lanes = v.reshape(4, nv)
     s = [0.0] * 4
@@ -662,39 +675,63 @@ def _group_find(v, x):
         q, (e, b, val) = nz
     else:
         q, (e, b, val) = 0, (0, exs[0], 0.0)
-    return q * nv + e, b, val
+    return q * nv + e, b, val, hit is None
 
 
-def per_sample_tree(prios, size, cap, beta, uniforms, alpha=0.6, tree=None):
-    """The device's draw (csrc/pm_per.h per_sample_block) for capacities <= 1M (one prefix round):
-    indices and un-normalised IS weights (size * P(i))^-beta, exactly as libpongmi computes them.
-    prios: the priorities the sample sees (pushes applied). Returns (idx int64, w f32)."""
+def per_sample_tree(prios, size, cap, beta, uniforms, alpha=0.6, tree=None, want_fallback=False):
+    """The device's draw (csrc/pm_per.h per_sample_block): indices and un-normalised IS weights
+    (size * P(i))^-beta, exactly as libpongmi computes them, at any size. The chunk sums are taken in
+    rounds of 1024: each round's inclusive prefix is formed on top of the running total of the rounds
+    before it (per_round_prefix), and the total a draw is scaled by is the running total after the
+    last round (above 1024 chunks the device forms it in a pass of its own, by the same additions).
+    A draw is searched for in the first round that has any mass and whose prefix exceeds u * total;
+    a round that has mass but no such entry leaves its last nonzero chunk as the fallback (`lastnz` /
+    `lastbef`), which the rounds after it replace and the draw takes if no round has a hit.
+    prios: the priorities the sample sees (pushes applied). Returns (idx int64, w f32), and with
+    want_fallback, per draw, which levels settled it by their last nonzero child because u * total had
+    been rounded onto or past that level's running total: bit 4 the chunk level (no round had a hit:
+    the carried `lastnz`), bit 2 the 16 nodes of the chunk, bit 1 the 64 leaves of the node."""
     chunk, sub, leaf = tree if tree is not None else per_tree(prios, cap, alpha)
-    nch = chunk.shape[0]
-    assert nch <= 1024, "one prefix round"
     nb = (size + PER_CHUNK - 1) // PER_CHUNK
-    vals = np.zeros(1024)
-    vals[:nb] = chunk[:nb]
-    incl, total = _round_prefix(vals)
+    rounds, run = [], 0.0
+    for c0 in range(0, nb, 1024):
+        n = min(1024, nb - c0)
+        vals = np.zeros(1024)
+        vals[:n] = chunk[c0:c0 + n]
+        incl, end = _round_prefix(vals, run)
+        rounds.append((c0, n, incl, run, end))
+        run = end
+    total = run
     idx = np.zeros(len(uniforms), np.int64)
     w = np.zeros(len(uniforms), np.float32)
+    fell = np.zeros(len(uniforms), np.int64)
     lf = np.asarray(leaf, np.float32)
     for j, u in enumerate(np.asarray(uniforms, np.float64)):
         x = u * total
-        k = int(np.searchsorted(incl[:nb] > x, True)) if np.any(incl[:nb] > x) else nb
-        if k < nb:
-            blk, before = k, (incl[k - 1] if k else 0.0)
-        else:
-            lo = int(np.argmax(incl[:nb] >= incl[nb - 1]))
-            blk, before = lo, (incl[lo - 1] if lo else 0.0)
+        blk, before, lastnz, lastbef = -1, 0.0, 0, 0.0
+        for c0, n, incl, run, end in rounds:
+            if blk >= 0 or not end > run:
+                continue
+            k = _bsearch(incl[:n] > x, 0, n)
+            if k < n:
+                blk, before = c0 + k, (incl[k - 1] if k else run)
+            else:  # the round's last nonzero chunk: the first to reach the round's end value
+                lo = _bsearch(incl[:n] >= incl[n - 1], 0, n - 1)
+                lastnz, lastbef = c0 + lo, (incl[lo - 1] if lo else run)
+        blk_fell = blk < 0
+        if blk_fell:
+            blk, before = lastnz, lastbef
         sv = np.array([sub[blk * 16 + e] if blk * 16 + e < sub.shape[0] else 0.0 for e in range(16)])
-        f1, b1, _ = _group_find(sv, x - before)
+        f1, b1, _, fb1 = _group_find(sv, x - before)
         sb = blk * 16 + f1
         e0 = sb * PER_SUB
         lv = np.array([float(lf[e0 + e]) if e0 + e < size else 0.0 for e in range(64)])
-        f0, _, pa = _group_find(lv, (x - before) - b1)
+        f0, _, pa, fb0 = _group_find(lv, (x - before) - b1)
+        fell[j] = 4 * blk_fell + 2 * fb1 + fb0
         idx[j] = e0 + f0
         w[j] = np.float32(((float(size) * (pa / total)) ** (-beta)))
+    if want_fallback:
+        return idx, w, fell
     return idx, w
 
 
@@ -708,6 +745,15 @@ def per_boundary_band(prios, size, uniforms, alpha=0.6, tol=5e-7):
     cdf = np.cumsum(p) / p.sum()
     u = np.asarray(uniforms, np.float64)
     return np.searchsorted(cdf, u - tol, side="right") != np.searchsorted(cdf, u + tol, side="right")
+
+
+def bits_equal(a, b):
+    """Arrays equal bit for bit (so -0.0 != 0.0), with the same shape and dtype."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    u = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize]
+    return np.array_equal(a.view(u), b.view(u))
 
 
 def per_update(prios, idxs, errors):
@@ -914,10 +960,12 @@ def sincos_serve(x):
     return s, c
 
 
-def philox_serve(params_dict, i, nserve, seed, step=None):
+def philox_serve(params_dict, i, nserve, seed, step=None, want_far=False):
     """The device's production serve (pm_dev.h serve_draw) restated: arrays i, nserve. With `step`
     (K1's step-keyed stream, ABI 15: pm_env_step's counter) the key is (i, TAG_SERVE_STEP, step lo,
-    step hi) and nserve is ignored."""
+    step hi) and nserve is ignored. want_far: also return the mask of serves whose |angle| >= 135
+    degrees, which the device redoes with OCML's sincos (serve_finish) and this restatement with
+    numpy's: those agree within the two libraries' rounding, every other serve bit for bit."""
     p = params_dict
     if step is None:
         r0 = philox(i, TAG_SERVE, nserve, 0, seed)
@@ -935,6 +983,8 @@ def philox_serve(params_dict, i, nserve, seed, step=None):
     sn, cs = sincos_serve(rad)
     far = ~(np.abs(rad) < 2.35619449019234483700)  # the device redoes these with OCML's sincos (< 1 ulp)
     sn, cs = np.where(far, np.sin(rad), sn), np.where(far, np.cos(rad), cs)
+    if want_far:
+        return speed * cs, speed * sn, spin, far
     return speed * cs, speed * sn, spin
 
 

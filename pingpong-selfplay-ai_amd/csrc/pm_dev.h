@@ -410,8 +410,12 @@ __device__ __forceinline__ double clip01(double v) { return v < 0.0 ? 0.0 : (v >
 
 // a / b for a divisor b with correctly rounded reciprocal inv = RN(1/b): q = RN(a*inv) is within an
 // ulp of a/b, and one FMA residual step q + RN(a - b*q)*inv rounds correctly (Markstein's theorem,
-// for results clear of under/overflow; checked against IEEE division on 2.4e8 random operands for
-// the divisors the configs produce). Zero dividends keep their sign, as a/b does.
+// for results clear of under/overflow). Pinned to the reference's own a / b, every bit and sign, on
+// the tables tests/golden/collide_kat.npz (m in {1, 2, 0.5}, where 1/m is exact) and collide_div.npz
+// (m in {3, 0.7, 1.7, 0.1, 7, 1e-3}, whose reciprocals round), each with I = (2/5) m R^2 for R in
+// {0.03, 0.05} and {0.03, 0.07, 0.0123, 0.5}, and on the trajectories of env_heavy.npz (m = 3,
+// R = 0.07) and of the at-scale runs with m = 1.7, R = 0.0123. Zero dividends keep their sign, as
+// a/b does.
 __device__ __forceinline__ double div_by(double a, double b, double inv) {
     const double q = a * inv;
     const double r = __builtin_fma(-q, b, a);

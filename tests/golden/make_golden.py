@@ -13,6 +13,7 @@ repository: only inputs and the reference's outputs are written, as .npz data.
 
 Fixtures:
   collide_kat.npz   envs/physics.py:3-23 known-answer table (stick / slide / +-0 vrel / int e)
+  collide_div.npz   the same over masses and radii whose reciprocals 1/m, 1/I are inexact
   env_<cfg>.npz     per-arena PongEnv2P trajectories (envs/my_pong_env_2p.py:83-232), serves drawn
                     from the global `random` stream after random.seed(seed_i)
   rollout_random.npz config-1 loop: random-vs-random with randint actions from the same stream
@@ -80,6 +81,20 @@ with open(os.path.join(REF, "config_rnn.yaml")) as f:
     PARAM_SETS["rnn"] = yaml.safe_load(f)["env"]
 # constructor defaults (envs/my_pong_env_2p.py:19-37): restitution 0.9 < 1, friction 0.2 -> slide-heavy
 PARAM_SETS["default"] = {}
+# The spin flag off while the serve spin and the Magnus factor are non-zero (the `if self.enable_spin`
+# of step(), :121-122): the spin still changes at every paddle hit and is still observed.
+PARAM_SETS["nospin"] = dict(enable_spin=False, magnus_factor=0.05, spin_range=(-10, 10), paddle_speed=0.03,
+                            max_score=2, ball_speed_range=(0.03, 0.05), speed_scale_every=2, speed_increment=0.1)
+# A paddle half the court wide whose step clips at both walls, friction 0 (|Jt*| <= 0 decides stick
+# or slide), restitution below 1 and a speed scale below 1.
+PARAM_SETS["wide"] = dict(paddle_width=0.5, paddle_speed=0.3, restitution=0.5, friction=0.0, max_score=1,
+                          speed_scale_every=2, speed_increment=-0.05, ball_speed_range=(0.04, 0.06))
+# Mass 3 and radius 0.07: 1/m and 1/I are inexact, so the divisions by m and I round. Stick-heavy
+# friction, restitution above 1, zero spin at serve, leftward serves (|angle| in [100, 170]).
+PARAM_SETS["heavy"] = dict(ball_mass=3.0, world_ball_radius=0.07, friction=1.5, restitution=1.2, magnus_factor=-0.02,
+                           paddle_width=0.35, paddle_speed=0.05, max_score=4, speed_scale_every=5,
+                           speed_increment=0.3, ball_angle_intervals=[[100, 170], [-170, -100]], spin_range=(0, 0),
+                           ball_speed_range=(0.02, 0.07))
 
 STATE_FIELDS = ["ball_x", "ball_y", "ball_vx", "ball_vy", "spin", "top_paddle_x", "bottom_paddle_x",
                 "scoreA", "scoreB", "bounce_count"]
@@ -129,6 +144,35 @@ def make_collide():
     np.savez_compressed(os.path.join(OUT, "collide_kat.npz"),
                         inputs=np.array(rows, dtype=np.float64), outputs=np.array(outs, dtype=np.float64))
     print("collide_kat", len(rows))
+
+
+def make_collide_div():
+    """collide_kat's rows over masses and radii whose reciprocals 1/m and 1/I are inexact (and a few
+    exact ones), so the two divisions of physics.py:20-21 round: the table a reciprocal-based
+    division has to reproduce."""
+    rng = np.random.RandomState(4321)
+    rows, outs = [], []
+    for i in range(4000):
+        vn = rng.uniform(-0.08, 0.08)
+        vt = rng.uniform(-0.08, 0.08)
+        u = [0.0, 0.03, -0.03, 0.02, -0.02][rng.randint(5)]
+        om = rng.uniform(-8, 8)
+        e = [1, 1.0, 0.9, 0.5, 1.2, 0.0][rng.randint(6)]
+        mu = [0.6, 0.2, 0.0, 1.5][rng.randint(4)]
+        m = [3.0, 0.7, 1.7, 0.1, 7.0, 1e-3][rng.randint(6)]
+        R = [0.03, 0.07, 0.0123, 0.5][rng.randint(4)]
+        rows.append((vn, vt, u, om, float(e), mu, m, R))
+        outs.append(ref_phys.collide_sphere_with_moving_plane(vn, vt, u, om, e, mu, m, R))
+    R = 0.03
+    for m in (1.0, 3.0):
+        for (vn, vt, u, om) in [(0.05, 0.0, 0.0, 0.0), (0.05, -0.0, 0.0, 0.0), (0.05, 0.0, -0.0, 0.0),
+                                (0.0, 0.01, 0.0, 0.0), (0.04, 0.03, 0.03, 0.0), (-0.04, 0.03, 0.03, -0.0)]:
+            for e in (1, 1.0, 0.9):
+                rows.append((vn, vt, u, om, float(e), 0.0, m, R))
+                outs.append(ref_phys.collide_sphere_with_moving_plane(vn, vt, u, om, e, 0.0, m, R))
+    np.savez_compressed(os.path.join(OUT, "collide_div.npz"),
+                        inputs=np.array(rows, dtype=np.float64), outputs=np.array(outs, dtype=np.float64))
+    print("collide_div", len(rows))
 
 
 # ------------------------------------------------------------------------- env trajectories
@@ -380,10 +424,11 @@ def make_per():
 
 
 if __name__ == "__main__":
-    make_collide()
-    for name in PARAM_SETS:
-        make_env(name)
-    make_rollout_random()
-    make_qnet()
-    make_dqn()
-    make_per()
+    # no argument: every fixture; otherwise the named ones (collide_kat, collide_div, env_<set>,
+    # rollout_random, qnet, dqn_steps, per), so a new fixture can be written without rewriting the others
+    makers = {"collide_kat": make_collide, "collide_div": make_collide_div, "rollout_random": make_rollout_random,
+              "qnet": make_qnet, "dqn_steps": make_dqn, "per": make_per}
+    makers.update({f"env_{name}": (lambda name=name: make_env(name)) for name in PARAM_SETS})
+    for which in sys.argv[1:] or ["collide_kat", "collide_div"] + [f"env_{n}" for n in PARAM_SETS] + \
+            ["rollout_random", "qnet", "dqn_steps", "per"]:
+        makers[which]()

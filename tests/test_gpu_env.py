@@ -25,7 +25,7 @@ def _state_matrix(env):
     return np.stack([np.asarray(st[k], np.float64) for k in STATE_ORDER], 1)
 
 
-@pytest.mark.parametrize("name", ["cfg", "rnn", "default"])
+@pytest.mark.parametrize("name", ["cfg", "rnn", "default", "nospin", "wide", "heavy"])
 def test_env_matches_reference_trajectories_bit_exact(golden, name):
     """All golden arenas stepped in one batch with the recorded actions; serves drawn host-side
     with CPython's random exactly as the reference (parity mode). Every fp64 state word, obs,
@@ -227,18 +227,24 @@ def test_collide_kat_bit_exact(golden):
     assert np.array_equal(np.signbit(got), np.signbit(g["outputs"]))
 
 
-def test_scalar_dropin_matches_reference_trajectories_bit_exact(golden):
-    """The scalar drop-in (envs/my_pong_env_2p.py PongEnv2P: one pm_env_reset1 / pm_env_step1 launch
-    per call, results read from host-mapped memory) replays the reference's own runs exactly as
-    make_golden.py recorded them: random.seed(seed_i), construct (one reset), then the recorded
-    actions with reset() on done — every observation, reward, done flag and fp64 state word."""
+def test_collide_div_bit_exact(golden):
+    """pm_collide over masses and radii whose reciprocals are inexact (tests/golden/collide_div.npz:
+    the reciprocal-plus-FMA division of pm_dev.h div_by has to round as the reference's a / b)."""
+    from envs.physics import collide_batch
+
+    g = golden("collide_div")
+    got = collide_batch(g["inputs"])
+    assert np.array_equal(got, g["outputs"])
+    assert np.array_equal(np.signbit(got), np.signbit(g["outputs"]))
+
+
+def _scalar_dropin_replay(g, arenas):
     import random
     from envs.my_pong_env_2p import PongEnv2P
 
-    g = golden("env_cfg")
     kw, _ = _kwargs_from_golden(g)
     n, T = g["actA"].shape
-    for i in range(min(n, 6)):
+    for i in range(min(n, arenas)):
         random.seed(int(g["seeds"][i]))
         env = PongEnv2P(**kw)
         assert np.array_equal(_state_matrix(env._env)[0], g["init"][i])
@@ -254,8 +260,26 @@ def test_scalar_dropin_matches_reference_trajectories_bit_exact(golden):
                 oA, oB = env.reset()
                 assert np.array_equal(oA, g["reset_obs"][i, t, 0]) and np.array_equal(oB, g["reset_obs"][i, t, 1])
                 assert np.array_equal(_state_matrix(env._env)[0], g["reset_state"][i, t]), (i, t)
+    return env
+
+
+def test_scalar_dropin_matches_reference_trajectories_bit_exact(golden):
+    """The scalar drop-in (envs/my_pong_env_2p.py PongEnv2P: one pm_env_reset1 / pm_env_step1 launch
+    per call, results read from host-mapped memory) replays the reference's own runs exactly as
+    make_golden.py recorded them: random.seed(seed_i), construct (one reset), then the recorded
+    actions with reset() on done — every observation, reward, done flag and fp64 state word."""
+    env = _scalar_dropin_replay(golden("env_cfg"), 6)
     with pytest.raises(ValueError):
         env.step(3, 0)
+
+
+@pytest.mark.parametrize("name", ["rnn", "default", "nospin", "wide", "heavy"])
+def test_scalar_dropin_matches_reference_parameter_sets_bit_exact(golden, name):
+    """The same replay through the scalar drop-in on the other five parameter sets, three arenas
+    each: spin off, a wide fast paddle with friction 0, mass 3 among them."""
+    g = golden(f"env_{name}")
+    assert g["done"][:3].sum() >= 3  # the three arenas do reach reset()
+    _scalar_dropin_replay(g, 3)
 
 
 def test_scalar_collide_dropin_kat_bit_exact(golden):
@@ -264,6 +288,16 @@ def test_scalar_collide_dropin_kat_bit_exact(golden):
     from envs.physics import collide_sphere_with_moving_plane
 
     g = golden("collide_kat")
+    got = np.array([collide_sphere_with_moving_plane(*[float(v) for v in r]) for r in g["inputs"]], np.float64)
+    assert np.array_equal(got, g["outputs"])
+    assert np.array_equal(np.signbit(got), np.signbit(g["outputs"]))
+
+
+def test_scalar_collide_dropin_div_bit_exact(golden):
+    """pm_collide1 on the inexact-reciprocal table, signed zeros included."""
+    from envs.physics import collide_sphere_with_moving_plane
+
+    g = golden("collide_div")
     got = np.array([collide_sphere_with_moving_plane(*[float(v) for v in r]) for r in g["inputs"]], np.float64)
     assert np.array_equal(got, g["outputs"])
     assert np.array_equal(np.signbit(got), np.signbit(g["outputs"]))

@@ -4,9 +4,12 @@ import numpy as np
 import pytest
 
 
+def _param_values(g):
+    return dict(zip([str(n) for n in g["param_names"]], g["param_values"].tolist()))
+
+
 def _params(orc, g):
-    names = [str(n) for n in g["param_names"]]
-    vals = dict(zip(names, g["param_values"].tolist()))
+    vals = _param_values(g)
     return vals, orc.make_params(vals)
 
 
@@ -19,7 +22,22 @@ def test_collide_kat_bit_exact(orc, golden):
     assert np.array_equal(np.signbit(g["outputs"]), np.signbit(np.array([orc.collide(*r.tolist()) for r in g["inputs"]])))
 
 
-@pytest.mark.parametrize("name", ["cfg", "rnn", "default"])
+def test_collide_div_bit_exact(orc, golden):
+    """The collision over masses and radii whose reciprocals are inexact (m in {3, 0.7, 1.7, 0.1, 7,
+    1e-3}, R in {0.03, 0.07, 0.0123, 0.5}: the divisions by m and I round), with the +-0 edge rows for
+    m = 1 and m = 3: every output word and sign bit of the reference's."""
+    g = golden("collide_div")
+    assert {3.0, 0.7, 1.7, 0.1, 7.0, 1e-3} <= set(g["inputs"][:, 6].tolist()) and len(g["inputs"]) >= 4000
+    got = np.array([orc.collide(*r.tolist()) for r in g["inputs"]])
+    assert np.array_equal(got, g["outputs"])
+    assert np.array_equal(np.signbit(got), np.signbit(g["outputs"]))
+    assert np.any(np.signbit(g["outputs"]) & (g["outputs"] == 0))  # the table does hold a -0.0
+
+
+ENV_SETS = ["cfg", "rnn", "default", "nospin", "wide", "heavy"]
+
+
+@pytest.mark.parametrize("name", ENV_SETS)
 def test_env_trajectories_bit_exact(orc, golden, name):
     """Oracle replays the reference trajectory: serves from a CPython-identical MT19937 stream
     seeded like random.seed(seed_i), steps with the recorded actions — every fp64 state word,
@@ -51,6 +69,22 @@ def test_env_fixture_covers_edge_events(golden):
     assert stick > 50 and slide > 20
     g = golden("env_cfg")
     assert g["done"].sum() > 20 and g["state"][..., 9].max() >= 5
+    # the parameter-space fixtures: each ends episodes and hits paddles, `wide` (friction 0) slides,
+    # `heavy` (friction 1.5) sticks
+    for n in ("nospin", "wide", "heavy"):
+        g = golden(f"env_{n}")
+        assert g["done"].sum() >= 10, n
+        assert int(g["hits_stick"]) + int(g["hits_slide"]) >= 1 and g["state"][..., 9].max() >= 1, n
+    assert int(golden("env_wide")["hits_slide"]) > 0 and int(golden("env_heavy")["hits_stick"]) > 0
+    # and each still holds what it is for
+    pv = {n: _param_values(golden(f"env_{n}")) for n in ("nospin", "wide", "heavy")}
+    assert pv["nospin"]["enable_spin"] == 0 and pv["nospin"]["magnus_factor"] != 0
+    assert np.abs(golden("env_nospin")["state"][..., 4]).max() > 0  # spin is there, only its Magnus term is off
+    w = golden("env_wide")["state"]  # both paddles clip at both walls
+    assert w[..., 5].min() == 0.0 and w[..., 5].max() == 1.0 and w[..., 6].min() == 0.0 and w[..., 6].max() == 1.0
+    assert pv["wide"]["friction"] == 0 and pv["wide"]["restitution"] < 1 and pv["wide"]["speed_increment"] < 0
+    assert pv["heavy"]["ball_mass"] == 3.0 and pv["heavy"]["restitution"] > 1  # 1/3 is inexact; leftward, spinless serves
+    assert np.all(golden("env_heavy")["init"][:, 2] < 0) and np.all(golden("env_heavy")["init"][:, 4] == 0)
 
 
 def test_rollout_random_matches_reference_loop(orc, golden):
@@ -208,7 +242,7 @@ def test_per_tree_restatement_matches_reference(orc, golden):
     assert draws >= 256
 
 
-@pytest.mark.parametrize("size", [1, 1023, 1025, 4096, 200_000, 1_000_000])
+@pytest.mark.parametrize("size", [1, 1023, 1025, 4096, 200_000, 1_000_000, 1_048_577, 2_097_153])
 def test_per_tree_restatement_vs_choice_outside_band(orc, size):
     """At every buffer size: the tree order and np.random.choice's float32-normalised CDF pick the same
     index for every uniform outside the CDF-boundary rounding band (per_boundary_band)."""
