@@ -653,8 +653,9 @@ int pm_selfplay_step(const pm_selfplay* sp, void* stream);
  *   pm_selfplay_learn_act: pm_selfplay_learn, plus side-A actions for the observations the last
  *     pm_selfplay_env wrote (the next vector step's), into sp->aA.
  *   pm_selfplay_actenv: act_part(B) + env fused into one launch (k_actenv): every 256-arena block
- *     computes modelB's greedy actions for its arenas on the matrix cores and ticks them; the PER
- *     sampler blocks also compute the batch rows k_env's forward blocks would. Bit-identical to
+ *     computes modelB's greedy actions for its arenas on the matrix cores and ticks them; the
+ *     ceil(batch / 8) PER sampler blocks (8 samples each) also compute the batch rows k_env's forward
+ *     blocks would, one 16-column tile per block (its samples' s and s' rows). Bit-identical to
  *     act_part(B) + env.
  *   pm_selfplay_step_overlap = actenv + learn_act + apply (unsharded).
  * Contract: before act_part(B) / actenv / step_overlap, sp->aA must hold side-A actions for the current

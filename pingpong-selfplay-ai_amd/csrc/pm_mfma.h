@@ -380,6 +380,48 @@ __device__ __forceinline__ void heads_finish(const float (&acc)[4], const float*
     q[2] = v + (a2 - mean);
 }
 
+// ----------------------------------------------------------------------------- 16-column tiles
+// The same forward on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain bit for bit as well,
+// tools/mfma_order_probe.hip): a wave owns 16 units of a layer for 16 columns, layer 1 is 2 MFMAs and
+// layer 2 is 16, and the layers hand over through LDS in the orders below (k_rollout16, k_actenv's
+// sampler blocks).
+// layer 2's k order: sequence position of unit u, and the unit at position q
+__device__ __forceinline__ int l2_pos(int u) {
+    const int t = u >> 5, v = u & 31, b = (v >> 2) & 1, r = (v & 3) + 4 * (v >> 3);
+    return 2 * (16 * t + r) + b;
+}
+__device__ __forceinline__ int l2_unit(int q) {
+    const int i = q >> 1, b = q & 1;
+    return 32 * (i >> 4) + rho(i & 15) + 4 * b;
+}
+// the head chains' order: unit u is element 16t + r of half (u >> 2) & 1's chain
+__device__ __forceinline__ int head_pos(int u) {
+    const int t = u >> 5, v = u & 31;
+    return 16 * t + (v & 3) + 4 * (v >> 3);
+}
+
+typedef float f32x4v16 __attribute__((ext_vector_type(4)));
+
+// Head weights (F_H order, 260 floats) by output: opw[set][h][j][q] = weight of output j (V, A0, A1,
+// A2) at chain position q of half h, the A operands of the heads' v_mfma_f32_4x4x1_f32 chain (one wave).
+template <int NSET>
+__device__ __forceinline__ void heads_to_opw(float (&opw)[NSET][2][4][32], int set, const float* hf) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int idx = it * 64 + lane, h = idx >> 7, j = (idx >> 5) & 3, q = idx & 31;
+        opw[set][h][j][q] = hf[(h * 32 + q) * 4 + j];
+    }
+}
+
+// v + (v of lane ^ 16) as v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3 exchanged between two copies)
+// instead of a ds_bpermute round trip, so each lane adds the same pair: the same bits as
+// v + __shfl_xor(v, 16) (an IEEE add commutes).
+__device__ __forceinline__ float xor16_sum(float v) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
 // layer-1 B operands of this lane for observation row o: input k' = 2s + h, k' = 0 -> 1.0 (bias),
 // k' >= 1 -> o[k' - 1]
 __device__ __forceinline__ void tile_inputs(const float* __restrict__ o, int h, float (&xs)[4]) {

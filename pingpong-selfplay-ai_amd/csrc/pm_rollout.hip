@@ -341,23 +341,8 @@ static __device__ unsigned long long pm_diag_roll[2][8];
     } while (0)
 #endif
 
-// layer 2's k order: sequence position of unit u, and the unit at position q
-__device__ __forceinline__ int l2_pos(int u) {
-    const int t = u >> 5, v = u & 31, b = (v >> 2) & 1, r = (v & 3) + 4 * (v >> 3);
-    return 2 * (16 * t + r) + b;
-}
-__device__ __forceinline__ int l2_unit(int q) {
-    const int i = q >> 1, b = q & 1;
-    return 32 * (i >> 4) + rho(i & 15) + 4 * b;
-}
-// the head chains' order: unit u is element 16t + r of half (u >> 2) & 1's chain
-__device__ __forceinline__ int head_pos(int u) {
-    const int t = u >> 5, v = u & 31;
-    return 16 * t + (v & 3) + 4 * (v >> 3);
-}
-
-typedef float f32x4v16 __attribute__((ext_vector_type(4)));
-
+// (l2_pos / l2_unit / head_pos, the layers' hand-over orders, f32x4v16, heads_to_opw and xor16_sum:
+// pm_mfma.h, shared with k_actenv's sampler blocks.)
 struct Roll16Shared {
     // the layer operands of the launch: every wave reads its own into registers once (2 + 16 + 4), so
     // no step re-reads them
@@ -382,25 +367,9 @@ struct Roll16Shared {
     __attribute__((aligned(16))) float opw[3][2][4][32];
 };
 
-// Head weights (F_H order, 260 floats) -> opw[set]: output-major per half (one wave).
-__device__ __forceinline__ void roll16_opw(Roll16Shared& sm, int set, const float* hf) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int idx = it * 64 + lane, h = idx >> 7, j = (idx >> 5) & 3, q = idx & 31;
-        sm.opw[set][h][j][q] = hf[(h * 32 + q) * 4 + j];
-    }
-}
-
 // The heads' cross-lane moves, on the gfx950 row / half swaps instead of ds_bpermute round trips on
-// wave 0's chain. xor16_sum: v + (v of lane ^ 16) as v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3
-// exchanged between two copies), so each lane adds the same pair: the same bits as
-// v + __shfl_xor(v, 16) (an IEEE add commutes). halves_bcast: lanes 0-31's value in both halves (lo)
+// wave 0's chain: xor16_sum (pm_mfma.h) and halves_bcast: lanes 0-31's value in both halves (lo)
 // and lanes 32-63's (hi), one v_permlane32_swap for both.
-__device__ __forceinline__ float xor16_sum(float v) {
-    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 __device__ __forceinline__ void halves_bcast(int v, int& lo, int& hi) {
     const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
     lo = (int)r[0];
@@ -475,8 +444,8 @@ __device__ __forceinline__ void rollout16_body(const pm_env_params& p, const pm_
             for (int k = 0; k < 7; ++k) sm.ob[g][col][k] = g ? oB[k] : oA[k];
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (wv == 7) roll16_opw(sm, 1, sm.hfB[0]);  // its own fetch of hfB[0] has landed (same wave)
-    if (wv == 6) roll16_opw(sm, 0, wA + PLAIN + F_H);  // modelA's heads straight from global
+    if (wv == 7) heads_to_opw(sm.opw, 1, sm.hfB[0]);  // its own fetch of hfB[0] has landed (same wave)
+    if (wv == 6) heads_to_opw(sm.opw, 0, wA + PLAIN + F_H);  // modelA's heads straight from global
     __syncthreads();
     // the wave's layer-1 and layer-2 A operands and layer-2 bias, constant over the launch
     const float4* im2 = reinterpret_cast<const float4*>(sm.img2[player][rt][0][lane]);
@@ -613,7 +582,7 @@ __device__ __forceinline__ void rollout16_body(const pm_env_params& p, const pm_
         } else if (wv == 2 && st + 1 < steps) {
             roll16_eps(sm, i, ctr + 1, (st + 1) & 1, eps, seed_env, g);
         } else if (wv == 7 && st + 1 < steps) {
-            roll16_opw(sm, 1 + ((st + 1) & 1), sm.hfB[(st + 1) & 1]);  // the next step's heads (landed before barrier B)
+            heads_to_opw(sm.opw, 1 + ((st + 1) & 1), sm.hfB[(st + 1) & 1]);  // the next step's heads (landed before barrier B)
         }
         __syncthreads();  // (C) the next observations
         ROLL_T(6);

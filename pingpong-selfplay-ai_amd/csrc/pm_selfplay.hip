@@ -324,22 +324,26 @@ __device__ __forceinline__ void env_fwd_block(const pm_selfplay& sp, int f, bool
     if (mine) store_hfeat(sp.hfeat, j, nxt, lane, c2, qb, qt, rb);
 }
 
-// The fused step's sampler blocks: block b draws samples [32 b, 32 b + 32) (per_sample_block) and then
-// computes their stable rows' forward itself: no other block waits for the sample. Its 4 waves split
-// the forward of the 2 tiles (s rows, s' rows) by layer-2 tile, as k_rollout_push does (pm_mfma.h
-// hidden_half / heads_half): wave 2 k + jt computes layer-2 tile jt of tile k (24 MFMAs deep instead of
-// 40); wave jt = 0 runs the head chains over its 32 units and hands the partial sums to wave jt = 1
-// through LDS, which continues them in tile_heads' order, so every stored value is bit-identical to
-// batch_row_fwd's. s rows need only Q_B (store_hfeat stores Q_T of s' rows only).
-struct SampleFwd32Smem {
+// The fused step's sampler blocks: block b draws samples [8 b, 8 b + 8) (per_sample_block) and then
+// computes their stable rows' forward itself, as one 16-column tile on v_mfma_f32_16x16x4_f32 in
+// k_rollout16's layout (pm_mfma.h "16-column tiles"): columns 0-7 are the samples' s rows, columns 8-15
+// their s' rows, so no other block waits for the sample and no descent runs twice. Wave rt owns units
+// 16 rt .. 16 rt + 15 of both layers: layer 1 is 2 MFMAs, layer 2 is 16, each handed on through LDS in
+// the next stage's k order; wave 0 then runs both head sets (learn_heads: Q_B on every column, Q_T for
+// the s' columns) as one chain of 32 v_mfma_f32_4x4x1_f32. Every accumulator chain has tile_hidden's /
+// tile_heads' k order, so every stored value is bit-identical to batch_row_fwd's (a wave's layer chain
+// is 18 MFMAs of 32 cycles, where the 32-row tiles split by layer-2 tile ran 40 of 64).
+constexpr int kSampBlock = 8;  // samples per sampler block: half a 16-column tile
+struct SampleFwd16Smem {
     PerSampleSmem per;
-    float lw[kLwFloats];
-    float hf[pad256(2 * 264)];
-    int64_t sidx[PER_BS / 2];
-    float part[2][64][8];  // [tile][lane]: Q_B chains 0..3, Q_T chains 4..7 after layer-2 tile 0
+    int64_t sidx[kSampBlock];
+    __attribute__((aligned(16))) float h1s[4][4][16][4];  // [g][s >> 2][col][s & 3]: layer-2 B of instruction s
+    __attribute__((aligned(16))) float c2s[2][8][16][4];  // [h][q >> 2][col][q & 3]: ReLU(layer 2), chain order
+    __attribute__((aligned(16))) float hf[pad256(2 * 264)];  // learn_heads: set 0 = Q_B's heads, set 1 = Q_T's
+    __attribute__((aligned(16))) float opw[2][2][4][32];     // [set]: heads_to_opw of hf[264 set ..]
 };
-__device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b, SampleFwd32Smem& sm) {
-    constexpr int NS = PER_BS / 2;
+__device__ __forceinline__ void sample_fwd_block16(const pm_selfplay& sp, int b, SampleFwd16Smem& sm) {
+    constexpr int NS = kSampBlock;
     // The control block is read once, here, in the chunk sums' round trip (sample_block's fields, with
     // the pending push): `active`, the push range of `mine` and beta all come from these values. A
     // second read after the descent is a dependent round trip in front of the row loads. pm_ctrl is
@@ -356,13 +360,28 @@ __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b,
     const PushRange pr = push_of(sp, cpos, csize, cmaxp);
     const double beta = beta_of(sp, frame);
     const uint64_t key = sp.seed_env;
-    // this lane's sample (q == 0 lanes of waves 0-1) as the descent leaves it: the leaf and the total
-    // of its IS weight, which is formed behind the row loads below (only k_learn reads isw)
+    const int lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
+    const int rt = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // this lane's sample (q == 0 lanes of wave 0's first half) as the descent leaves it: the leaf and
+    // the total of its IS weight, which is formed behind the row loads below (only k_learn reads isw)
     int wj = -1;
     double wpa = 0.0, wtot = 1.0;
-    // the forward's weights are staged once the top level of the descent is done: LDS DMA in flight
-    // makes hipcc wait vmcnt(0) at the next use of a plain load, which would put the 20 KB staging in
-    // front of the chunk-sum round trip
+    // The wave's A operands come from w_B's fragment image (pm_mfma.h F_W1 / F_W2, the 32-row tiles'
+    // operand order: the same floats as the plain weights). A 16 x 16 x 4 lane (row 16 rt + col, k group g)
+    // finds its operands there as whole float4s: layer 1's two (input k' = g and 4 + g) are elements
+    // g >> 1 and 2 + (g >> 1) of the row's F_W1 quad in lane half g & 1; layer 2's instruction i
+    // multiplies unit l2_unit(4 i + g), which is element 2 (i & 1) + (g >> 1) of F_W2 quad
+    // (t = i >> 3, rq = (i & 7) >> 1) of the same row and lane half. So a wave loads 9 float4s whose
+    // lanes form two 256-byte runs each (36 cache lines; gathering the 18 floats from the plain weights
+    // touched 16 lines per load and held the level-1 loads behind it back by 1.3 us), plus the b2 quad
+    // its accumulator starts from. They and the LDS DMA of the two head sets are issued once the top
+    // level of the descent is done: in front of the chunk sums they would stand in their round trip
+    // (with LDS DMA in flight hipcc waits vmcnt(0) at the next use of a plain load). Nothing here is
+    // consumed before the level-1 loads are: a load used inside the hook would hold its wave for a round
+    // trip of its own.
+    float4 f1 = make_float4(0.f, 0.f, 0.f, 0.f), f2[8], b2r = f1;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) f2[m] = f1;
     per_sample_block<true>(
         active, size, per_tree(sp.per_work, sp.cap), pr, beta, b * NS, min(sp.batch, b * NS + NS), sm.per,
         [&](int j) {
@@ -377,69 +396,124 @@ __device__ __forceinline__ void sample_fwd_block32(const pm_selfplay& sp, int b,
             wtot = total;
         },
         [&] {
-            stage_frags_lds(sp.w_B, sm.lw, b * 5);
+            const float* w = sp.w_B;
+            const int jt = rt >> 1, fl = 32 * (g & 1) + 16 * (rt & 1) + col;  // the row's tile and fragment lane
+            f1 = reinterpret_cast<const float4*>(w + PLAIN + F_W1)[jt * 64 + fl];
+            const float4* q2 = reinterpret_cast<const float4*>(w + PLAIN + F_W2) + jt * 8 * 64 + fl;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) f2[m] = q2[m * 64];
+            b2r = *reinterpret_cast<const float4*>(w + B2 + 16 * rt + 4 * g);
             copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
         });
     if (!active) return;  // block-uniform
-    __syncthreads();  // sidx, staged weights
+    __syncthreads();  // sidx, the staged heads
     PM_BLK(1);
-    const int lane = threadIdx.x & 63, B = sp.batch;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool nxt = (wv >> 1) != 0;  // wave-uniform: tile 0 = s rows, tile 1 = s' rows
-    const int jt = wv & 1;
-    const int j = b * NS + (lane & 31);
+    const int B = sp.batch;
+    const bool nxt = col >= NS;  // columns 0-7: s rows, 8-15: s' rows of the same samples
+    const int j = b * NS + (col & (NS - 1));
     const int64_t id = sm.sidx[min(j, B - 1) - b * NS];
     const bool mine = j < B && !pr.covers(id);
-    // The row's six loads (4 layer-1 inputs, reward, action|done bits), then the weight. In this order
-    // hipcc issues the six back to back (no vmcnt wait among them; with the pow in front of them it
-    // reused the first load's register and waited for it before the other four) and starts the
-    // weight's fp64 code after the last: plain source order, no fence and no select needed (a select
-    // for tile_inputs' conditional o[0] plus a scheduling fence measured the same).
-    const int h = lane >> 5;
-    float xs[4];
+    // The row's loads (the lane's two layer-1 inputs, then reward and action|done bits, which only wave
+    // 0 stores: behind a wave-uniform branch they cost every wave a vmcnt(0) at its second input), then
+    // the weight: in this order hipcc issues the loads back to back and starts the weight's fp64 code
+    // after the last. The weight is stored at the block's end: vmcnt counts stores, and a store between
+    // the loads and layer 1 would have its acknowledgement waited for there.
     const float* tr = sp.trans + id * PM_TRANS_F;
-    tile_inputs(tr + (nxt ? 8 : 0), h, xs);
+    const float* o = tr + (nxt ? 8 : 0);
+    const float o0 = o[g == 0 ? 0 : g - 1];
+    const float x1 = o[3 + g];
     const float rb0 = tr[7], rb1 = tr[15];
-    if (wj >= 0) sp.isw[wj] = per_is_weight(size, wpa, wtot, beta);
-    f32x16 c2;
-    hidden_half(sm.lw, xs, lane, jt, c2);
-    const float* hf0 = sm.hf;
-    const float* hf1 = sm.hf + 264;
-    float ab[4] = {0.f, 0.f, 0.f, 0.f}, at[4] = {0.f, 0.f, 0.f, 0.f};
-    float* row = sp.hfeat + (size_t)j * 80;
-    if (jt == 0) {
-        heads_half(hf0, c2, lane, 0, ab);
-        if (nxt) heads_half(hf1, c2, lane, 0, at);
-        *reinterpret_cast<float4*>(&sm.part[nxt][lane][0]) = make_float4(ab[0], ab[1], ab[2], ab[3]);
-        if (nxt) *reinterpret_cast<float4*>(&sm.part[nxt][lane][4]) = make_float4(at[0], at[1], at[2], at[3]);
-    }
-    if (mine && !nxt) {
+    // waves 2-3 (their lanes hold no sample) rearrange one head set each by output, under the row loads
+    if (rt >= 2) heads_to_opw(sm.opw, rt - 2, sm.hf + (rt - 2) * 264);
+    float wisw = 0.f;
+    if (wj >= 0) wisw = per_is_weight(size, wpa, wtot, beta);
+    // this lane's elements of the quads (selects, under the row loads)
+    const bool odd = (g >> 1) != 0;
+    const float w1r[2] = {odd ? f1.y : f1.x, odd ? f1.w : f1.z};
+    float w2r[16];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) row[32 * jt + rho(q) + 4 * h] = relu(c2[q]);
+    for (int m = 0; m < 8; ++m) {
+        w2r[2 * m] = odd ? f2[m].y : f2[m].x;
+        w2r[2 * m + 1] = odd ? f2[m].w : f2[m].z;
     }
-    __syncthreads();  // the chains over layer-2 tile 0
-    if (jt == 0) return;
+    // layer 1, the wave's row tile (K 8: bias + 7 inputs, input k' = 4 s + g) -> ReLU -> LDS
     {
-        const float4 pa = *reinterpret_cast<const float4*>(&sm.part[nxt][lane][0]);
-        ab[0] = pa.x; ab[1] = pa.y; ab[2] = pa.z; ab[3] = pa.w;
+        const float x0 = g == 0 ? 1.0f : o0;
+        const f32x4v16 zero = {0.f, 0.f, 0.f, 0.f};
+        f32x4v16 c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1r[0], x0, zero, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1r[1], x1, c1, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // unit 16 rt + 4 g + r -> its slot in layer 2's k order
+            const int q = l2_pos(16 * rt + 4 * g + r), sq = q >> 2;
+            sm.h1s[q & 3][sq >> 2][col][sq & 3] = relu(c1[r]);
+        }
     }
-    heads_half(hf0, c2, lane, 1, ab);
-    float qb[3], qt[3];
-    heads_finish(ab, hf0, qb);
-    if (nxt) {
-        const float4 pt = *reinterpret_cast<const float4*>(&sm.part[nxt][lane][4]);
-        at[0] = pt.x; at[1] = pt.y; at[2] = pt.z; at[3] = pt.w;
-        heads_half(hf1, c2, lane, 1, at);
-        heads_finish(at, hf1, qt);
+    __syncthreads();  // layer 1, opw
+    // lane 32 set + 16 h + 4 cg + j's head A operands, the weights of output j of the set's half h, and
+    // the set's biases: wave 0's, read here so that they retire under layer 2 (every wave reads them: a
+    // wave-uniform branch costs the other waves 36 register clears at its join)
+    float hw4[32];
+    {
+        const float* src = sm.opw[lane >> 5][(lane >> 4) & 1][lane & 3];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float4 w = *reinterpret_cast<const float4*>(src + 4 * k);
+            hw4[4 * k] = w.x; hw4[4 * k + 1] = w.y; hw4[4 * k + 2] = w.z; hw4[4 * k + 3] = w.w;
+        }
     }
-    if (mine && h == 0) {
-        if (!nxt) {
-            row[64] = qb[0]; row[65] = qb[1]; row[66] = qb[2];
-            row[67] = rb0;  // reward
-            row[71] = rb1;  // action | done << 8 (float bits)
-        } else {
-            row[68] = qb[0]; row[69] = qb[1]; row[70] = qb[2];
-            row[72] = qt[0]; row[73] = qt[1]; row[74] = qt[2];
+    const float4 bhr = *reinterpret_cast<const float4*>(sm.hf + (lane >> 5) * 264 + 256);
+    float bs[16];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 v = *reinterpret_cast<const float4*>(sm.h1s[g][k][col]);
+        bs[4 * k] = v.x; bs[4 * k + 1] = v.y; bs[4 * k + 2] = v.z; bs[4 * k + 3] = v.w;
+    }
+    f32x4v16 c2 = {b2r.x, b2r.y, b2r.z, b2r.w};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) c2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w2r[i], bs[i], c2, 0, 0, 0);
+    float* row = sp.hfeat + (size_t)j * 80;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int u = 16 * rt + 4 * g + r, q = head_pos(u);
+        c2[r] = relu(c2[r]);
+        sm.c2s[(u >> 2) & 1][q >> 2][col][q & 3] = c2[r];
+    }
+    // the features of s, by unit index: units 16 rt + 4 g .. + 3 of the row are this lane's accumulator
+    if (mine && !nxt) *reinterpret_cast<float4*>(row + 16 * rt + 4 * g) = make_float4(c2[0], c2[1], c2[2], c2[3]);
+    __syncthreads();  // layer 2
+    if (rt != 0) return;
+    if (wj >= 0) sp.isw[wj] = wisw;  // wave 0's lanes
+    // Heads on the matrix cores, as k_rollout16's wave 0: lane block (set, h, column group) multiplies
+    // the 4 outputs' weights by 4 columns' ReLU(layer 2), so lane 32 set + 16 h + col ends with the four
+    // partial sums of tile_heads' half chains of its column, in tile_heads' fmaf order.
+    const int set = lane >> 5, hh = (lane >> 4) & 1;
+    float xb[32];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float4 x = *reinterpret_cast<const float4*>(sm.c2s[hh][k][col]);
+        xb[4 * k] = x.x; xb[4 * k + 1] = x.y; xb[4 * k + 2] = x.z; xb[4 * k + 3] = x.w;
+    }
+    f32x4v16 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 32; ++q) acc = __builtin_amdgcn_mfma_f32_4x4x1f32(hw4[q], xb[q], acc, 0, 0, 0);
+    // + the other half (both lanes get the same bits), the biases, Q = V + (A - mean(A))
+    float v = xor16_sum(acc[0]), a0 = xor16_sum(acc[1]), a1 = xor16_sum(acc[2]), a2 = xor16_sum(acc[3]);
+    v += bhr.x;
+    a0 += bhr.y;
+    a1 += bhr.z;
+    a2 += bhr.w;
+    const float mean = ((a0 + a1) + a2) / 3.0f;  // A.mean(dim=1)
+    const float q0 = v + (a0 - mean), q1 = v + (a1 - mean), q2 = v + (a2 - mean);
+    if (mine && hh == 0) {
+        if (set == 0) {  // Q_B
+            float* qd = row + (nxt ? 68 : 64);
+            qd[0] = q0; qd[1] = q1; qd[2] = q2;
+            if (!nxt) {
+                row[67] = rb0;  // reward
+                row[71] = rb1;  // action | done << 8 (float bits)
+            }
+        } else if (nxt) {  // Q_T, stored for s' only
+            row[72] = q0; row[73] = q1; row[74] = q2;
         }
     }
 }
@@ -671,19 +745,19 @@ __global__ __launch_bounds__(kBlock) void k_env(const pm_selfplay sp) {
     env_block<false>(sp, blk, sm, nullptr);
 }
 
-// The fused step's first kernel (pm_selfplay_actenv): blocks [0, ceil(B/32)) sample the update's batch
-// and compute its stable rows (sample_fwd_block32); every other block acts for modelB and ticks its 256
+// The fused step's first kernel (pm_selfplay_actenv): blocks [0, ceil(B/8)) sample the update's batch
+// and compute its stable rows (sample_fwd_block16); every other block acts for modelB and ticks its 256
 // arenas (env_block<true>). Replaces k_act_sp(PM_ACT_B) + k_env of the overlapped step, bit for bit.
 union ActEnvShared {
     ActEnvSmem ae;
-    SampleFwd32Smem sf32;
+    SampleFwd16Smem sf16;
 };
 __global__ __launch_bounds__(kBlock) void k_actenv(const pm_selfplay sp) {
     __shared__ __attribute__((aligned(16))) ActEnvShared sh;
-    const int nsb = (sp.batch + 31) / 32;  // sampler blocks, PER_BS / 2 samples each
+    const int nsb = (sp.batch + kSampBlock - 1) / kSampBlock;  // sampler blocks, 8 samples each
     if ((int)blockIdx.x < nsb) {
         PM_BLK(0);
-        sample_fwd_block32(sp, (int)blockIdx.x, sh.sf32);
+        sample_fwd_block16(sp, (int)blockIdx.x, sh.sf16);
         PM_BLK_END();
         return;
     }
@@ -982,7 +1056,7 @@ struct PushFwdSmem {
 };
 
 // push_rows_fwd on block 1's 16 waves, two per 32-row tile (hidden_half / heads_half, as
-// sample_fwd_block32): wave 2k + jt computes layer-2 tile jt of tile 8 it + k (24 MFMAs deep instead
+// k_rollout_push): wave 2k + jt computes layer-2 tile jt of tile 8 it + k (24 MFMAs deep instead
 // of 40); wave jt = 0 runs the head chains over its 32 units and hands them to wave jt = 1 through
 // LDS, which continues them in tile_heads' order. Bit-identical rows to push_rows_fwd.
 __device__ __forceinline__ void push_rows_fwd2(const pm_selfplay& sp, PushFwdSmem& sm, int wv, int lane, float* pay,
@@ -2799,7 +2873,7 @@ extern "C" int pm_selfplay_env(const pm_selfplay* sp, void* stream) {
 extern "C" int pm_selfplay_actenv(const pm_selfplay* sp, void* stream) {
     int rc = check(sp);
     if (rc) return rc;
-    const unsigned nsb = pm_blocks(sp->batch, 32);  // sampler blocks (sample_fwd_block32)
+    const unsigned nsb = pm_blocks(sp->batch, kSampBlock);  // sampler blocks (sample_fwd_block16)
     pm_launch(PM_TIMER_ACTENV, k_actenv, dim3(nsb + pm_blocks(sp->n, kBlock)), dim3(kBlock), pm_stream(stream), *sp);
     PM_LAUNCHED("k_actenv");
     return PM_OK;

@@ -40,7 +40,7 @@ def main():
     nb = (n + 255) // 256
     buf = (ctypes.c_uint64 * (8 * 1024))()
     blk = (ctypes.c_uint64 * (8 * 4096))()
-    nsb = (256 + 31) // 32  # k_actenv's sampler blocks: 32 samples each
+    nsb = (256 + 7) // 8  # k_actenv's sampler blocks: 8 samples each (sample_fwd_block16)
     acc, samp, staged = [], [], []
     for _ in range(20):
         if L.overlap:  # the production step's launches, read right after the fused act + env kernel
