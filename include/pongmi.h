@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define PM_ABI_VERSION 26
+#define PM_ABI_VERSION 27
 
 #define PM_OK 0
 #define PM_E_ARG (-1)     /* null / inconsistent argument */
@@ -380,6 +380,62 @@ int pm_drqn_apply(const pm_drqn *d, void *stream);
  * store. pm_drqn_apply after an all-reduce forms the same shares of the summed gradient in the same
  * order (round 6), so with one rank the two paths give bit-identical parameters, clip active or not. */
 int pm_drqn_update(const pm_drqn *d, void *stream);
+
+/* ---------------------------------------------------------------- stand-alone double-DQN learner (K10) */
+
+/* train_step (scripts/train_iterative.py:141-168) on a batch the caller supplies (ABI 27; csrc/pm_dqn.hip):
+ * q = Q_B(s)[a]; a* = argmax Q_B(s') (first maximum); t = r + gamma * Q_T(s')[a*] * (1 - done), targetB
+ * in eval mode (mu only); L = mean(isw * (q - t)^2); torch.optim.Adam; targetB <- modelB when the step
+ * count, after its increment, is a multiple of target_update_interval. With train_features = 0 only the
+ * 520 head parameters train (the reference freezes modelB.features, :97) and params, adam_m / adam_v and
+ * grad keep their bits in [0, PM_QNET_HEAD_OFF). With train_features = 1 the backward runs on through
+ * both ReLU layers (relu'(0) = 0) and Adam covers all PM_DQN_NPARAM slots, in the parameter block's
+ * order. The gradient is a pure function of the inputs: every sum has one fixed order, there is no
+ * atomic, and nothing in the launch waits for another workgroup. Rows at or past `batch` are not read.
+ * Both blocks, grad and the moments are 16-byte aligned. */
+#define PM_DQN_NPARAM 5192
+typedef struct pm_dqn_stats {
+    int64_t steps;  /* updates taken (train_steps: the target sync and the noise counter) */
+    int64_t adam_t; /* the optimizer's step count (bias correction) */
+    float loss;     /* loss of the last batch (this replica's) */
+    float q_mean;   /* mean q of the last batch */
+    int32_t status; /* reserved: nothing in the update can time out */
+    int32_t _pad;
+} pm_dqn_stats;
+
+typedef struct pm_dqn {
+    float *params, *target;       /* [PM_QNET_NP] modelB / targetB blocks (pongmi.qnet layout) */
+    float *adam_m, *adam_v;       /* [PM_DQN_NPARAM]; heads-only mode touches [4672, 5192) only */
+    float *grad;                  /* [PM_DQN_NPARAM + 8]: gradients, then [PM_DQN_NPARAM] = 1 per contributing
+                                     rank (summed by the all-reduce) and 7 zeros */
+    pm_dqn_stats *stats;          /* device */
+    const float *s, *ns;          /* [batch][7] */
+    const int32_t *act;           /* [batch] in {0, 1, 2} */
+    const float *rew;             /* [batch] */
+    const uint8_t *done;          /* [batch] */
+    const float *isw;             /* nullable [batch] importance weights: null = all ones */
+    float *td;                    /* [batch] |q - t| (update_priorities' errors, :163) */
+    float *q;                     /* nullable [batch][3]: Q_B(s) as used by the loss */
+    int32_t batch;                /* 1..PM_MAX_BATCH */
+    int32_t train_features;       /* 0: heads only (the reference); 1: all PM_DQN_NPARAM parameters */
+    int32_t noise;                /* PM_FOLD_TRAIN: the block's epsilon buffers as they are;
+                                     PM_FOLD_TRAIN_FRESH: reset_noise() first (:142): Philox(seed_net,
+                                     TAG_NOISE_TRAIN, stats->steps + 1) as the fused learner draws it, the
+                                     counter read on the device, the noise written into params' epsilon
+                                     buffers */
+    int32_t _pad;
+    int64_t target_update_interval;
+    double gamma, lr, beta1, beta2, adam_eps;
+    uint64_t seed_net;
+} pm_dqn;
+
+/* The three forwards, loss, td and grad (grad[PM_DQN_NPARAM] <- 1); stats->loss / q_mean written. */
+int pm_dqn_grads(const pm_dqn* d, void* stream);
+/* grad / grad[PM_DQN_NPARAM] -> Adam -> target sync -> stats->steps / adam_t + 1. Nothing happens when
+ * grad[PM_DQN_NPARAM] == 0. */
+int pm_dqn_apply(const pm_dqn* d, void* stream);
+/* pm_dqn_grads then pm_dqn_apply on one replica, as one launch (the same arithmetic: bit-identical). */
+int pm_dqn_update(const pm_dqn* d, void* stream);
 
 /* ---------------------------------------------------------------- QNetRNN self-play (K7) */
 
@@ -762,7 +818,7 @@ const char* pm_last_error(void);
 int pm_abi_version(void);
 int32_t pm_sizeof(int32_t which); /* 0: pm_env_params 1: pm_env_state 2: pm_ctrl 3: pm_selfplay 4: pm_drqn
                                      5: pm_drqn_stats 6: pm_rnn_ctrl 7: pm_rnn_selfplay
-                                     8: pm_roll_replay */
+                                     8: pm_roll_replay 9: pm_dqn 10: pm_dqn_stats */
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,8 @@ extern "C" int32_t pm_sizeof(int32_t which) {
         case 6: return (int32_t)sizeof(pm_rnn_ctrl);
         case 7: return (int32_t)sizeof(pm_rnn_selfplay);
         case 8: return (int32_t)sizeof(pm_roll_replay);
+        case 9: return (int32_t)sizeof(pm_dqn);
+        case 10: return (int32_t)sizeof(pm_dqn_stats);
         default: return -1;
     }
 }

@@ -42,11 +42,10 @@ __device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 __device__ __forceinline__ float relu(float x) { return __int_as_float(max(__float_as_int(x), 0)); }
 
 // ----------------------------------------------------------------------------- fragment writers
-// Feature fragments (W1, W2, b1, b2) + the plain feature copy, from a parameter block. Block-wide.
-__device__ __forceinline__ void write_feature_frags(const float* __restrict__ p, float* __restrict__ w) {
+// Feature fragments (F_W1, F_W2, F_B1, F_B2) from a parameter block into the fragment image at f
+// (global or LDS). Block-wide.
+__device__ __forceinline__ void write_feature_frag_image(const float* __restrict__ p, float* __restrict__ f) {
     const int t = threadIdx.x, nt = blockDim.x;
-    for (int k = t; k < PM_QNET_HEAD_OFF; k += nt) w[k] = p[k];
-    float* f = w + PLAIN;
     for (int k = t; k < 512; k += nt) {  // W1
         const int jt = k >> 8, lane = (k >> 2) & 63, s = k & 3;
         const int row = 32 * jt + (lane & 31), kk = 2 * s + (lane >> 5);
@@ -62,6 +61,11 @@ __device__ __forceinline__ void write_feature_frags(const float* __restrict__ p,
         f[F_B1 + k] = p[B1 + 32 * jt + rho(r) + 4 * h];
         f[F_B2 + k] = p[B2 + 32 * jt + rho(r) + 4 * h];
     }
+}
+// The plain feature copy + the feature fragments of an effective-weight block w. Block-wide.
+__device__ __forceinline__ void write_feature_frags(const float* __restrict__ p, float* __restrict__ w) {
+    for (int k = threadIdx.x; k < PM_QNET_HEAD_OFF; k += blockDim.x) w[k] = p[k];
+    write_feature_frag_image(p, w + PLAIN);
 }
 
 // Head fragments + plain head slice from 260 folded head values (Wh [4][64] | bh [4]). Block-wide.
@@ -229,9 +233,10 @@ __device__ __forceinline__ void heads_to_frags(const float* heads, float* hf) {
 // xs: this lane's layer-1 B operands, input k' = 2s + (lane>>5) with k' = 0 the constant 1.0 (its
 // weight column is b1) and k' = 1..7 the observation. The fma chain per output is b1 + W·x in
 // k order, as with a bias-initialised accumulator. lw: staged fragments.
-__device__ __forceinline__ void tile_hidden(const float* lw, const float (&xs)[4], int lane, f32x16 (&c2)[2]) {
+// c1: ReLU(layer 1) in the accumulator layout (the update's backward keeps it).
+__device__ __forceinline__ void tile_hidden_h1(const float* lw, const float (&xs)[4], int lane, f32x16 (&c1)[2],
+                                               f32x16 (&c2)[2]) {
     const int h = lane >> 5;
-    f32x16 c1[2];
     const f32x16 zero = {};
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt) {
@@ -270,6 +275,10 @@ __device__ __forceinline__ void tile_hidden(const float* lw, const float (&xs)[4
         wcur = wnext;
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+__device__ __forceinline__ void tile_hidden(const float* lw, const float (&xs)[4], int lane, f32x16 (&c2)[2]) {
+    f32x16 c1[2];
+    tile_hidden_h1(lw, xs, lane, c1, c2);
 }
 
 // Dueling heads (VALU) on ReLU(c2): this lane holds 32 of the 64 hidden rows of its column; the two

@@ -31,13 +31,14 @@ PM_QNET_PLAIN = 4936
 PM_RNN_NP = 192012
 PM_RNN_NPARAM = 174984
 PM_RNN_NW = 157456
+PM_DQN_NPARAM = 5192
 PM_TRANS_F = 16
 PM_MAX_BATCH = 256
 PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
-ABI_VERSION = 26
+ABI_VERSION = 27
 PM_GB_NONE, PM_GHEADS_LEN = 3, 264
 PM_TIMER_ACTENV, PM_TIMER_LEARN, PM_TIMER_RNN_ACT, PM_TIMER_ENV_STEP, PM_TIMER_ROLLOUT, PM_TIMER_DRQN = 0, 1, 2, 3, 4, 5
 PM_TIMER_LEARN_MULTI, PM_TIMER_N = 6, 7
@@ -94,6 +95,20 @@ class Drqn(ctypes.Structure):
         [("batch", c_i32), ("T", c_i32), ("target_update_interval", c_i64)] + \
         [(n, c_double) for n in ("gamma", "lr", "beta1", "beta2", "adam_eps", "max_norm")] + \
         [("poll_limit", c_i32), ("reserved", c_i32)]
+
+
+class DqnStats(ctypes.Structure):
+    _fields_ = [("steps", c_i64), ("adam_t", c_i64), ("loss", c_float), ("q_mean", c_float), ("status", c_i32),
+                ("_pad", c_i32)]
+
+
+class Dqn(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("params", "target", "adam_m", "adam_v", "grad", "stats", "s", "ns", "act",
+                                        "rew", "done", "isw", "td", "q")] + \
+        [("batch", c_i32), ("train_features", c_i32), ("noise", c_i32), ("_pad", c_i32),
+         ("target_update_interval", c_i64)] + \
+        [(n, c_double) for n in ("gamma", "lr", "beta1", "beta2", "adam_eps")] + \
+        [("seed_net", c_u64)]
 
 
 class RnnCtrl(ctypes.Structure):
@@ -158,6 +173,9 @@ _SIGS = {
     "pm_drqn_grads": (c_i32, [c_void_p, c_void_p]),
     "pm_drqn_apply": (c_i32, [c_void_p, c_void_p]),
     "pm_drqn_update": (c_i32, [c_void_p, c_void_p]),
+    "pm_dqn_grads": (c_i32, [c_void_p, c_void_p]),
+    "pm_dqn_apply": (c_i32, [c_void_p, c_void_p]),
+    "pm_dqn_update": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_act": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_env": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -230,7 +248,7 @@ def load():
     if L.pm_abi_version() != ABI_VERSION:
         raise PongmiError(f"libpongmi ABI {L.pm_abi_version()} != {ABI_VERSION}")
     for which, cls in ((0, EnvParams), (1, EnvState), (2, Ctrl), (3, SelfPlay), (4, Drqn), (5, DrqnStats), (6, RnnCtrl),
-                       (7, RnnSelfPlay)):
+                       (7, RnnSelfPlay), (8, RollReplay), (9, Dqn), (10, DqnStats)):
         if L.pm_sizeof(which) != ctypes.sizeof(cls):
             raise PongmiError(f"struct layout mismatch for {cls.__name__}: C {L.pm_sizeof(which)} "
                               f"vs ctypes {ctypes.sizeof(cls)}")

@@ -1,0 +1,171 @@
+"""The stand-alone double-DQN learner (K10): train_step (scripts/train_iterative.py:141-168) on a batch
+the caller supplies.
+
+DQNLearner owns modelB's and targetB's packed QNet blocks (pongmi.qnet layout), the Adam moments and
+the batch buffers; update() runs one train_step on (s, a, r, s', done[, isw]) as one pm_dqn_update
+call — modelB on s and s', targetB (eval mode) on s', the double-DQN target, the importance-weighted
+squared loss, the backward, Adam and the target sync — with no host synchronisation, and returns the
+device tensor of |q - t| for pongmi.replay.per_update. It is the update a caller with a replay of
+their own runs; the fused self-play step (pongmi.selfplay.SelfPlayLearner) keeps its own.
+
+train_features=False trains the 520 NoisyNet head parameters, as the reference does (it freezes
+modelB.features, :97); train_features=True trains all 5 192 parameters of the QNet.
+
+For data-parallel training, grads() / apply() split the update around the gradient all-reduce: every
+rank computes its gradient into `grad` ([PM_DQN_NPARAM] gradients, then a 1 marking a contributing
+rank), the ranks sum `grad`, then apply() divides by that count and takes the identical Adam step.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from ._lib import PM_DQN_NPARAM, PM_MAX_BATCH, PM_QNET_HEAD_OFF, PM_QNET_NP, check, stream_ptr
+from .checkpoint import adam_moments, adam_state_dict
+from .qnet import PARAM_LAYOUT, fold, pack_state_dict, unpack_state_dict
+
+ALL_SHAPES = [s for _, s in PARAM_LAYOUT[:12]]   # modelB.parameters() order
+HEAD_SHAPES = [s for _, s in PARAM_LAYOUT[4:12]]  # list(fc_V.parameters()) + list(fc_A.parameters()) (:101-104)
+
+
+class DQNLearner:
+    def __init__(self, modelB, target=None, *, batch=256, gamma=0.99, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8,
+                 target_update_interval=1000, train_features=False, fresh_noise=True, seed=0, device="cuda"):
+        """modelB / target: a QNet module, its state_dict, or a packed [PM_QNET_NP] tensor; target None = a
+        copy of modelB (copy.deepcopy(modelB), :100). batch: the most rows an update takes (1..256)."""
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        self.batch = int(batch)
+        if not 1 <= self.batch <= PM_MAX_BATCH:
+            raise ValueError(f"DQNLearner: batch {self.batch} (1..{PM_MAX_BATCH})")
+        self.train_features = bool(train_features)
+        self.params = self._block(modelB)
+        self.target = self._block(target) if target is not None else self.params.clone()
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.adam_m = torch.zeros(PM_DQN_NPARAM, **f32)
+        self.adam_v = torch.zeros(PM_DQN_NPARAM, **f32)
+        self.grad = torch.zeros(PM_DQN_NPARAM + 8, **f32)
+        self.stats_buf = torch.zeros(ctypes.sizeof(_lib.DqnStats), dtype=torch.uint8, device=self.device)
+        self.s = torch.zeros((self.batch, 7), **f32)
+        self.ns = torch.zeros((self.batch, 7), **f32)
+        self.act = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        self.rew = torch.zeros(self.batch, **f32)
+        self.done = torch.zeros(self.batch, dtype=torch.uint8, device=self.device)
+        self.isw = torch.ones(self.batch, **f32)
+        self.td = torch.zeros(self.batch, **f32)
+        self.q = torch.zeros((self.batch, 3), **f32)
+        d = _lib.Dqn()
+        for name in ("params", "target", "adam_m", "adam_v", "grad", "s", "ns", "act", "rew", "done", "td", "q"):
+            setattr(d, name, getattr(self, name).data_ptr())
+        d.stats = self.stats_buf.data_ptr()
+        d.isw = None
+        d.batch = self.batch
+        d.train_features = int(self.train_features)
+        d.noise = _lib.PM_FOLD_TRAIN_FRESH if fresh_noise else _lib.PM_FOLD_TRAIN
+        d.target_update_interval = int(target_update_interval)
+        d.gamma, d.lr, d.beta1, d.beta2, d.adam_eps = float(gamma), float(lr), float(betas[0]), float(betas[1]), \
+            float(eps)
+        d.seed_net = int(seed)
+        self.desc = d
+
+    def _block(self, m):
+        if isinstance(m, torch.Tensor):
+            if m.numel() != PM_QNET_NP:
+                raise ValueError(f"packed QNet block must have {PM_QNET_NP} floats")
+            return m.detach().to(self.device, torch.float32).reshape(-1).clone()
+        sd = m.state_dict() if hasattr(m, "state_dict") else m
+        return pack_state_dict(sd, self.device)
+
+    def load_batch(self, s, a, r, ns, done, isw=None):
+        """Copy a batch of n <= batch rows (any device / dtype) into the learner's input buffers."""
+        s = torch.as_tensor(s)
+        n = int(s.reshape(-1, 7).shape[0])
+        if not 1 <= n <= self.batch:
+            raise ValueError(f"DQNLearner: {n} rows (1..{self.batch})")
+        self.s[:n].copy_(s.reshape(n, 7))
+        self.ns[:n].copy_(torch.as_tensor(ns).reshape(n, 7))
+        self.act[:n].copy_(torch.as_tensor(a).reshape(n))
+        self.rew[:n].copy_(torch.as_tensor(r).reshape(n))
+        self.done[:n].copy_(torch.as_tensor(done).reshape(n))
+        if isw is not None:
+            self.isw[:n].copy_(torch.as_tensor(isw).reshape(n))
+        self.desc.isw = self.isw.data_ptr() if isw is not None else None
+        self.desc.batch = n
+
+    def _call(self, fn, stream=None):
+        check(fn(ctypes.byref(self.desc), stream_ptr(stream)), fn.__name__)
+
+    def update(self, *batch, isw=None, stream=None):
+        """One train_step; batch = (s, a, r, ns, done[, isw]) or nothing (buffers already filled).
+        Returns |q - t| per row (a view of the device buffer `td`): update_priorities' errors (:163)."""
+        if batch:
+            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
+        self._call(self.lib.pm_dqn_update, stream)
+        return self.td[:self.desc.batch]
+
+    def grads(self, *batch, isw=None, stream=None):
+        if batch:
+            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
+        self._call(self.lib.pm_dqn_grads, stream)
+        return self.td[:self.desc.batch]
+
+    def apply(self, stream=None):
+        self._call(self.lib.pm_dqn_apply, stream)
+
+    # ------------------------------------------------------------------ state
+    def _stats(self):
+        return _lib.DqnStats.from_buffer_copy(bytes(self.stats_buf.cpu().numpy()))
+
+    def _set_stats(self, **kw):
+        s = self._stats()
+        for k, v in kw.items():
+            setattr(s, k, v)
+        self.stats_buf.copy_(torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8))
+
+    def stats(self):
+        """(steps, adam_t, loss, mean q) of the last update (host sync)."""
+        s = self._stats()
+        return dict(steps=s.steps, adam_t=s.adam_t, loss=s.loss, q_mean=s.q_mean, status=s.status)
+
+    def state_dict(self):
+        """modelB's state_dict (reference key names; the epsilon buffers hold the last update's noise)."""
+        return unpack_state_dict(self.params)
+
+    def target_state_dict(self):
+        return unpack_state_dict(self.target)
+
+    def acting_weights(self, mode=_lib.PM_FOLD_EVAL, seed=0, counter=0):
+        """pongmi.qnet.fold of the current modelB block ([PM_QNET_NW]), for pongmi.qnet.act / q_values."""
+        return fold(self.params, mode, seed=seed, counter=counter)[0]
+
+    def load_params(self, modelB, target=None):
+        """modelB <- state; targetB <- target (default: a copy of the new modelB)."""
+        self.params.copy_(self._block(modelB))
+        self.target.copy_(self._block(target) if target is not None else self.params)
+
+    # ------------------------------------------------------------------ optimizer / counters
+    def _opt_layout(self):
+        return (ALL_SHAPES, 0) if self.train_features else (HEAD_SHAPES, PM_QNET_HEAD_OFF)
+
+    def optimizer_state_dict(self):
+        """torch.optim.Adam(...).state_dict() over modelB.parameters() (train_features) or over the
+        reference's list(fc_V.parameters()) + list(fc_A.parameters()) (:101-104)."""
+        shapes, off = self._opt_layout()
+        return adam_state_dict(shapes, self.adam_m[off:], self.adam_v[off:], self._stats().adam_t, self.desc.lr,
+                               (self.desc.beta1, self.desc.beta2), self.desc.adam_eps)
+
+    def load_optimizer_state_dict(self, sd):
+        shapes, off = self._opt_layout()
+        m, v, step = adam_moments(sd, shapes)
+        self.adam_m[off:].copy_(m)
+        self.adam_v[off:].copy_(v)
+        self._set_stats(adam_t=step)
+
+    def new_optimizer(self):
+        """optim.Adam(..., lr=lr): zero moments, step 0."""
+        self.adam_m.zero_()
+        self.adam_v.zero_()
+        self._set_stats(adam_t=0)
+
+    def set_train_steps(self, steps):
+        self._set_stats(steps=int(steps))
