@@ -260,9 +260,44 @@ template <bool WT>
 __device__ __forceinline__ void st_f4(float4* p, float4 v) {
     if constexpr (WT) {
         const pm_f4v x = {v.x, v.y, v.z, v.w};
-        asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(x) : "memory");
+        // s_nop 1 inside the string: a store of more than 8 bytes reads its data registers up to two wait
+        // states after issue, and hipcc pads nothing behind an asm statement (its next instruction wrote
+        // .x of the row pieces in store_ring_rows16: one float of four wrong in blocks that share a CU)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
     } else {
         *p = v;
+    }
+}
+
+// A wave's 64 ring rows of 16 floats (lane l holds row r0 + l as four float4 pieces) out as whole
+// lines: the pieces cross the wave's own 4 KB of LDS (no block barrier: a wave runs its LDS
+// instructions in order, the wavefront fences only keep the compiler from moving them), and lane l
+// stores piece l & 3 of row r0 + (l >> 2) + 16 k in instruction k, so one instruction writes 1 KB
+// contiguous (16 whole rows) instead of 64 lines with 16 B each. The slot is (pos + row) mod cap per
+// stored row (pos < cap, row < n <= cap: one conditional subtract), so the ring may wrap anywhere
+// inside the wave; a row at or past n is not stored. Every lane of the wave calls this, valid or not.
+template <bool WT>
+__device__ __forceinline__ void store_ring_rows16(float* __restrict__ ring, int64_t pos, int64_t cap, int r0, int n,
+                                                  float4 (*stage)[4], const float4 (&piece)[4]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) stage[lane][k] = piece[k];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const float4* flat = &stage[0][0];
+    float4 x[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = flat[lane + 64 * k];
+    // all four reads issued back to back, one wait (left alone, each sinks behind its store's branch)
+    asm volatile("" : "+v"(x[0].x), "+v"(x[1].x), "+v"(x[2].x), "+v"(x[3].x));
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 v = x[k];
+        const int row = r0 + (lane >> 2) + 16 * k;
+        int64_t slot = pos + row;
+        if (slot >= cap) slot -= cap;
+        if (row < n) st_f4<WT>(reinterpret_cast<float4*>(ring + slot * 16) + (lane & 3), v);
     }
 }
 

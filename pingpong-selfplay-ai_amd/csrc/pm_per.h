@@ -66,6 +66,54 @@ __device__ __forceinline__ double wave_incl_scan(double v, int lane) {
     return v;
 }
 
+// wave_incl_scan without the LDS crossbar (each __shfl_up of a double is two ds_bpermute round trips,
+// twelve on the chain): the same Hillis-Steele steps, at step o lane L adds the value lane L - o held
+// before the step, so every lane's sum has the same association and the same bits. Offsets 1, 2, 4, 8
+// are o DPP wave_shr:1 moves (a whole-wave shift, zeros shifted in: row_shr cannot cross a 16-lane
+// row); 16 and 32 are the gfx950 row / half swaps. Lanes below o add the +0.0 shifted in where the
+// loop adds nothing: the same bits for every value but -0.0, which a sum that starts at +0.0 never
+// is. Full waves only. Used by per_round_prefix alone (multi_update keeps wave_incl_scan).
+__device__ __forceinline__ double wave_shr1_f64(double v) {
+    const unsigned long long x = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)x, 0x138, 0xF, 0xF, true);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(x >> 32), 0x138, 0xF, 0xF, true);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_incl_scan_dpp(double v, int lane) {
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+        double u = v;
+#pragma unroll
+        for (int s = 0; s < o; ++s) u = wave_shr1_f64(u);
+        v += u;
+    }
+    const int row = lane >> 4;
+    {   // o = 16: rows (r0, r1, r2, r3) -> (0, r0, r1, r2)
+        const unsigned long long x = (unsigned long long)__double_as_longlong(v);
+        unsigned w[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned d = (unsigned)(x >> (32 * h));
+            const auto p = __builtin_amdgcn_permlane16_swap(d, d, false, false);  // [0] = (r0, r0, r2, r2), [1] = (r1, r1, r3, r3)
+            const auto m = __builtin_amdgcn_permlane32_swap(p[1], p[1], false, false);  // [0] = (r1, r1, r1, r1)
+            w[h] = row == 0 ? 0u : (row == 2 ? m[0] : p[0]);
+        }
+        v += __longlong_as_double((long long)(((unsigned long long)w[1] << 32) | w[0]));
+    }
+    {   // o = 32: (r0, r1, r2, r3) -> (0, 0, r0, r1)
+        const unsigned long long x = (unsigned long long)__double_as_longlong(v);
+        unsigned w[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const unsigned d = (unsigned)(x >> (32 * h));
+            const auto p = __builtin_amdgcn_permlane32_swap(d, d, false, false);  // [0] = (r0, r1, r0, r1)
+            w[h] = row < 2 ? 0u : p[0];
+        }
+        v += __longlong_as_double((long long)(((unsigned long long)w[1] << 32) | w[0]));
+    }
+    return v;
+}
+
 // Tree nodes of granularity g (entries per node) overlapping the ring range [pos, pos + n) mod cap:
 // ids a0 .. a0 + na - 1 (the part up to cap) then 0 .. nb - 1 (the wrapped part). Overlaps between
 // the two segments only repeat a node (same value written twice).
@@ -188,7 +236,7 @@ __device__ __forceinline__ double per_chunk_sum(const PerTree& t, int64_t c) {
 // index whose running sum of p exceeds u (searchsorted 'right'). Here a 256-thread block draws
 // PER_BS = 64 samples at once, descending the tree in three dependent load round trips:
 //   level 2: the block loads every chunk sum once (4 per thread), forms their inclusive prefix in LDS
-//            (one block scan) and each sample binary-searches it for t = u * total;
+//            (one block scan) and each sample searches it for t = u * total (per_lds_search);
 //   level 1: 4 lanes per sample read the chosen chunk's 16 sub sums (4 each), a 4-lane scan finds
 //            the sub-block;
 //   level 0: the same 4 lanes read its 64 leaves (16 each, one float4 x4 load) and find the entry.
@@ -211,9 +259,8 @@ __device__ inline double per_round_prefix(const double (&v)[4], double base, Per
     double run[4], acc = 0.0;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { acc += v[e]; run[e] = acc; }
-    const double incl = wave_incl_scan(acc, lane);
-    double excl = __shfl_up(incl, 1);
-    if (lane == 0) excl = 0.0;
+    const double incl = wave_incl_scan_dpp(acc, lane);
+    const double excl = wave_shr1_f64(incl);  // lane 0: 0.0
     if (lane == 63) sm.wsum[wv] = incl;
     __syncthreads();
     double wb = base;
@@ -226,15 +273,32 @@ __device__ inline double per_round_prefix(const double (&v)[4], double base, Per
     return tot;
 }
 
-// First k in [0, n) with sm.incl[k] > x (n if none).
+// First k in [0, n) with sm.incl[k] > x (n if none). Like the binary search it replaced, this is
+// that k only where sm.incl is non-decreasing over [0, n). per_round_prefix does not prove it: a
+// thread's values are (wb + excl) + run[e] while the next thread starts from the wave scan's sum of
+// the same terms in another association, so two neighbours across a thread boundary can invert by
+// an ulp of the running total (priorities spanning more than 2^53 make that ulp larger than a chunk
+// sum). x then has to fall inside that one-ulp gap for any search to depend on its probe positions;
+// base-4 and binary probes may then pick different chunks, each with a prefix value above x.
 __device__ __forceinline__ int per_lds_search(const PerSampleSmem& sm, int n, double x) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sm.incl[mid] > x) hi = mid;
-        else lo = mid + 1;
+    // Five rounds of three independent probes (strides 256, 64, 16, 4, 1) instead of ten dependent
+    // ones: the prefix is non-decreasing, so the probes that are not above x are a prefix of each
+    // round's and their count is the round's base-4 digit of k. An index at or past n counts as above
+    // x (its read is clamped), which leaves k = n when no value is.
+    static_assert(PER_ROUND == 1024, "per_lds_search's five base-4 digits");
+    int base = 0;
+#pragma unroll
+    for (int stride = 256; stride >= 1; stride >>= 2) {
+        const int np = stride == 256 ? 4 : 3;  // the first round also probes the last value: k = n when none is above x
+        double v[4];
+#pragma unroll
+        for (int i = 0; i < np; ++i) v[i] = sm.incl[min(base + stride * (i + 1) - 1, n - 1)];
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < np; ++i) cnt += (base + stride * (i + 1) - 1 < n && !(v[i] > x)) ? 1 : 0;
+        base += stride * cnt;
     }
-    return lo;
+    return base;
 }
 
 // 4-lane group search over the group's 4 x NV values (lane q of the group holds values

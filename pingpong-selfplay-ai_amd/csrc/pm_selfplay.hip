@@ -130,9 +130,13 @@ constexpr int kFeatTilesAct = 8, kFeatTilesLearn = 16;
 // The env blocks' replay rows, state and observation rows go out write-through (pm_dev.h st_out):
 // none of it is re-read from this L2 before the kernel boundary. PM_ENV_WT=0 builds plain stores.
 #ifndef PM_ENV_WT
-#define PM_ENV_WT 6
+#define PM_ENV_WT 7
 #endif
 constexpr bool kEnvWTRows = (PM_ENV_WT & 1) != 0, kEnvWTState = (PM_ENV_WT & 2) != 0, kEnvWTObs = (PM_ENV_WT & 4) != 0;
+constexpr bool kEnvWTPrio = (PM_ENV_WT & 8) != 0;  // prios and the PER leaf of the pushed rows
+// frow (the U > 1 path's feature rows): eight 16-byte pieces per lane at a 32-byte stride, the narrow
+// pattern that write-through makes slower; plain stores, as they were while bit 1 was off
+constexpr bool kEnvWTFrow = (PM_ENV_WT & 16) != 0;
 __host__ __device__ inline int feat_ntiles(int n) { return (n + 31) / 32; }
 
 // Actions ahead (ABI 26): the fused U = 1 learner launch hands k_actenv modelB's greedy ACTIONS for the
@@ -525,6 +529,7 @@ __device__ __forceinline__ void write_opp_lists(const pm_selfplay& sp, OppListSm
 
 struct EnvSmem {
     float lds[2][kBlock][7];
+    float4 rows[kBlock][4];  // the replay rows' way to whole-line stores, 4 KB per wave (wave-private)
     long long red[kBlock / 64][6];
     OppListSmem ol;
 };
@@ -655,7 +660,7 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
                     for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
                         for (int q4 = 0; q4 < 4; ++q4)  // units 32 jt + 8 q4 + 4 h + 0..3
-                            st_f4<kEnvWTRows>(fr + 8 * jt + 2 * q4,
+                            st_f4<kEnvWTFrow>(fr + 8 * jt + 2 * q4,
                                               make_float4(relu(fc2[k][jt][4 * q4]), relu(fc2[k][jt][4 * q4 + 1]),
                                                           relu(fc2[k][jt][4 * q4 + 2]), relu(fc2[k][jt][4 * q4 + 3])));
                 }
@@ -688,19 +693,23 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
         }
     }
     int onew = o;
-    if (valid) {
-        // memory.push((oB, aB, rB, nB, done)) (:243, :56-63)
-        int64_t slot = pos + i;  // pos < cap and i < n <= cap: one conditional subtract is the modulo
-        if (slot >= sp.cap) slot -= sp.cap;  // (a per-lane 64-bit % is a ~100-instruction expansion)
+    {
+        // memory.push((oB, aB, rB, nB, done)) (:243, :56-63): the wave's 64 rows as whole lines, every
+        // lane taking part (pm_dev.h store_ring_rows16; a lane past n holds arena n - 1's values, which
+        // are stored nowhere).
         // write-through (pm_dev.h st_out): the ring is re-read only by later samples, and the state and
         // observation rows only by later launches, so none of it stays dirty in L2 for the boundary
-        float4* row = reinterpret_cast<float4*>(sp.trans + slot * PM_TRANS_F);
-        st_f4<kEnvWTRows>(row + 0, make_float4(oB[0], oB[1], oB[2], oB[3]));
-        st_f4<kEnvWTRows>(row + 1, make_float4(oB[4], oB[5], oB[6], rB));
-        st_f4<kEnvWTRows>(row + 2, make_float4(nB[0], nB[1], nB[2], nB[3]));
-        st_f4<kEnvWTRows>(row + 3, make_float4(nB[4], nB[5], nB[6], __int_as_float(aB | (d << 8))));
-        sp.prios[slot] = maxp;
-        leaf[slot] = pval;
+        static_assert(PM_TRANS_F == 16, "store_ring_rows16 writes 64-byte rows");
+        const float4 piece[4] = {make_float4(oB[0], oB[1], oB[2], oB[3]), make_float4(oB[4], oB[5], oB[6], rB),
+                                 make_float4(nB[0], nB[1], nB[2], nB[3]),
+                                 make_float4(nB[4], nB[5], nB[6], __int_as_float(aB | (d << 8)))};
+        store_ring_rows16<kEnvWTRows>(sp.trans, pos, sp.cap, i0 + 64 * wv, sp.n, sm.rows + 64 * wv, piece);
+    }
+    if (valid) {
+        int64_t slot = pos + i;  // pos < cap and i < n <= cap: one conditional subtract is the modulo
+        if (slot >= sp.cap) slot -= sp.cap;  // (a per-lane 64-bit % is a ~100-instruction expansion)
+        st_out<kEnvWTPrio>(&sp.prios[slot], maxp);
+        st_out<kEnvWTPrio>(&leaf[slot], pval);
         float ernew = er;
         if (d) {  // next episode: the opponent and serve drawn above
             onew = onext;
