@@ -399,7 +399,13 @@ typedef struct pm_dqn_stats {
     int64_t adam_t; /* the optimizer's step count (bias correction) */
     float loss;     /* loss of the last batch (this replica's) */
     float q_mean;   /* mean q of the last batch */
-    int32_t status; /* reserved: nothing in the update can time out */
+    int32_t status; /* 0 from pm_dqn_grads / apply / update (nothing in them can time out). Latched by
+                       pm_dqn_replay_update, cleared by the caller:
+                       bit 0: an update was void because the replay's sum tree has no mass (all priorities
+                              zero or NaN);
+                       bit 1: a NaN |q - t| was stored as a priority (its leaf is 0), as pm_ctrl.status bit 1;
+                       bit 2: an update was void because a drawn slot lay outside [0, size) (the tree handed
+                              over was not current) */
     int32_t _pad;
 } pm_dqn_stats;
 
@@ -436,6 +442,45 @@ int pm_dqn_grads(const pm_dqn* d, void* stream);
 int pm_dqn_apply(const pm_dqn* d, void* stream);
 /* pm_dqn_grads then pm_dqn_apply on one replica, as one launch (the same arithmetic: bit-identical). */
 int pm_dqn_update(const pm_dqn* d, void* stream);
+
+/* The same update drawn from a device replay (csrc/pm_dqn_replay.hip), `updates` times in one call, on the
+ * stream, with no host synchronisation or copy. Per update: frame = d->stats->steps + 1 (read on the
+ * device: frame_idx += 1 before sampling, :136), beta = min(1, beta_start + frame (1 - beta_start) /
+ * beta_frames); d->batch slots drawn from the sum tree in per_work (pm_per_sample's draw over the fill
+ * `size`; uniform j of update k is u[k * batch + j], or with u null u53(Philox(j, TAG_PER, frame, seed)),
+ * the fused learner's convention); the weights (size P(i))^-beta divided in float32 by their maximum; the
+ * sampled rows of trans copied into d's OWN batch buffers s, ns, act, rew, done and isw (written here
+ * although pm_dqn declares them const; isw must not be null) and the slots into idx; pm_dqn_update's
+ * update, bit for bit; prios[idx[j]] = td[j] + 1e-6f (the last duplicate in batch order wins), their
+ * leaves, and the level-1 and level-2 tree nodes over them recomputed, so that per_work again equals a
+ * pm_per_build of prios bit for bit and the next update, or the next call, draws from it as it is.
+ * An update whose tree has no mass, or that draws a slot outside [0, size), is void: nothing is gathered,
+ * there is no Adam step, no steps increment and no scatter, every idx[j] is -1 and stats->status latches
+ * bit 0 or bit 2; a NaN td latches bit 1 (pm_dqn_stats). PM_E_ARG: a null descriptor or buffer (d->isw
+ * included), trans or per_work not 16-byte aligned, and whatever pm_dqn_update rejects; PM_E_SIZE: size <=
+ * 0, size > cap, updates <= 0, beta_frames <= 0. */
+typedef struct pm_dqn_replay {
+    float *trans;          /* [cap][PM_TRANS_F] ring (DeviceReplay.trans), 16-byte aligned */
+    float *prios;          /* [cap] */
+    void *per_work;        /* pm_per_work_bytes(cap): the sum tree over cap, current on entry, 16-byte aligned */
+    int64_t *idx;          /* [d->batch] out: the last update's sampled slots */
+    const double *u;       /* nullable [updates][d->batch]: the draws' uniforms (tests); null = Philox */
+    int64_t cap, size;     /* 0 < size <= cap: entries [0, size) are filled */
+    double alpha, beta_start;
+    int64_t beta_frames;   /* > 0 */
+    uint64_t seed;
+} pm_dqn_replay;
+size_t pm_dqn_replay_sizeof(void);
+int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates, void* stream);
+
+/* memory.push (:56-63) of n caller transitions, 0 < n <= cap, all device buffers: transition i goes to slot
+ * (pos + i) mod cap as a PM_TRANS_F row, prios = prio (the caller's max(prios), 1 while empty), leaf =
+ * prio^alpha, then the tree nodes overlapping the ring range are recomputed: per_work equals a pm_per_build
+ * of prios bit for bit when it did before. act must hold 0..2 (the low 8 bits are stored). PM_E_ARG: a null
+ * buffer, trans or per_work not 16-byte aligned; PM_E_SIZE: cap <= 0, n <= 0, n > cap, pos outside [0, cap). */
+int pm_replay_push(float* trans, float* prios, void* per_work, int64_t cap, int64_t pos, float alpha, float prio,
+                   const float* s, const int32_t* act, const float* rew, const float* ns, const uint8_t* done,
+                   int32_t n, void* stream);
 
 /* ---------------------------------------------------------------- QNetRNN self-play (K7) */
 

@@ -401,6 +401,17 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqn_update(const pm_dqn d) {
     dqn_apply_body(d, ak);
 }
 
+// pm_dqn_replay_update's middle launch: k_dqn_update on the batch k_dqr_sample gathered, or nothing when
+// that update is void (the sampler wrote -1 slots).
+__global__ __launch_bounds__(kDqn, 1) void k_dqr_update(const pm_dqn d, const int64_t* gate) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    if (gate[0] < 0) return;  // block-uniform
+    dqn_grads_body(d, sm);
+    __syncthreads();
+    dqn_apply_body(d, ak);
+}
+
 int check(const pm_dqn* d) {
     PM_REQUIRE(d, PM_E_ARG, "pm_dqn: null descriptor");
     PM_REQUIRE(d->params && d->target && d->adam_m && d->adam_v && d->grad && d->stats, PM_E_ARG, "pm_dqn: null buffer");
@@ -425,6 +436,14 @@ int dqn_apply(const pm_dqn* d, void* stream) {
 }
 
 }  // namespace
+
+int dqn_check(const pm_dqn* d) { return check(d); }
+
+int dqn_launch_update_gated(const pm_dqn* d, const int64_t* gate, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqr_update, dim3(1), dim3(kDqn), 0, st, *d, gate);
+    PM_LAUNCHED("k_dqr_update");
+    return PM_OK;
+}
 }  // namespace pm
 
 using namespace pm;

@@ -5,7 +5,8 @@
   pongmi.qnet      QNet parameter blocks + fused two-player acting (K2)
   pongmi.replay    prioritized replay sampling / priority update (K4)
   pongmi.selfplay  SelfPlayLearner: the batched train_iterative loop (K1+K2+K4+K3)
-  pongmi.dqn       DQNLearner: train_step on a caller's batch, heads only or the whole QNet (K10)
+  pongmi.dqn       DQNLearner: train_step on a caller's batch, heads only or the whole QNet (K10), or drawn
+                   from a DeviceReplay (update_from, K11); ReplayTrainer: collect and train
 """
 from ._lib import PongmiError, load  # noqa: F401
 

@@ -111,6 +111,12 @@ class Dqn(ctypes.Structure):
         [("seed_net", c_u64)]
 
 
+class DqnReplay(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("trans", "prios", "per_work", "idx", "u")] + \
+        [("cap", c_i64), ("size", c_i64), ("alpha", c_double), ("beta_start", c_double), ("beta_frames", c_i64),
+         ("seed", c_u64)]
+
+
 class RnnCtrl(ctypes.Structure):
     _fields_ = [("step", c_u64), ("episodes", c_i64), ("seq_count", c_i64), ("seq_size", c_i64), ("epsilon", c_double),
                 ("win_A", c_i64), ("ep_A", c_i64), ("win_P", c_i64), ("ep_P", c_i64), ("reward_B", c_double),
@@ -176,6 +182,10 @@ _SIGS = {
     "pm_dqn_grads": (c_i32, [c_void_p, c_void_p]),
     "pm_dqn_apply": (c_i32, [c_void_p, c_void_p]),
     "pm_dqn_update": (c_i32, [c_void_p, c_void_p]),
+    "pm_dqn_replay_sizeof": (ctypes.c_size_t, []),
+    "pm_dqn_replay_update": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
+    "pm_replay_push": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_act": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_env": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -252,6 +262,9 @@ def load():
         if L.pm_sizeof(which) != ctypes.sizeof(cls):
             raise PongmiError(f"struct layout mismatch for {cls.__name__}: C {L.pm_sizeof(which)} "
                               f"vs ctypes {ctypes.sizeof(cls)}")
+    if L.pm_dqn_replay_sizeof() != ctypes.sizeof(DqnReplay):  # additive to ABI 27: its own size function
+        raise PongmiError(f"struct layout mismatch for DqnReplay: C {L.pm_dqn_replay_sizeof()} "
+                          f"vs ctypes {ctypes.sizeof(DqnReplay)}")
     _lib = L
     return L
 

@@ -7,6 +7,9 @@ call — modelB on s and s', targetB (eval mode) on s', the double-DQN target, t
 squared loss, the backward, Adam and the target sync — with no host synchronisation, and returns the
 device tensor of |q - t| for pongmi.replay.per_update. It is the update a caller with a replay of
 their own runs; the fused self-play step (pongmi.selfplay.SelfPlayLearner) keeps its own.
+update_from() runs the same update on batches drawn from a pongmi.replay.DeviceReplay on the device
+(pm_dqn_replay_update: draw, gather, update, priority scatter, incremental tree refresh), and
+ReplayTrainer alternates it with the collecting rollout.
 
 train_features=False trains the 520 NoisyNet head parameters, as the reference does (it freezes
 modelB.features, :97); train_features=True trains all 5 192 parameters of the QNet.
@@ -54,6 +57,7 @@ class DQNLearner:
         self.isw = torch.ones(self.batch, **f32)
         self.td = torch.zeros(self.batch, **f32)
         self.q = torch.zeros((self.batch, 3), **f32)
+        self.idx = torch.zeros(self.batch, dtype=torch.int64, device=self.device)  # update_from's sampled slots
         d = _lib.Dqn()
         for name in ("params", "target", "adam_m", "adam_v", "grad", "s", "ns", "act", "rew", "done", "td", "q"):
             setattr(d, name, getattr(self, name).data_ptr())
@@ -102,6 +106,32 @@ class DQNLearner:
             self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
         self._call(self.lib.pm_dqn_update, stream)
         return self.td[:self.desc.batch]
+
+    def update_from(self, replay, updates=1, *, beta_start=0.4, beta_frames=100000, seed=0, uniforms=None, stream=None):
+        """`updates` train_steps drawn from a pongmi.replay.DeviceReplay in one pm_dqn_replay_update call:
+        per update the PER draw of `batch` slots (beta from stats.steps + 1, read on the device), the
+        gather of their rows into this learner's batch buffers, the update, and the priorities written
+        back with the sum tree refreshed where they changed — no host synchronisation, and the replay's
+        tree stays current (no refresh() needed). uniforms: float64 [updates, batch] to replay given
+        draws; None draws u53(Philox(j, TAG_PER, frame, seed)). Returns (idx, td) of the last update as
+        device tensors (views of `idx` / `td`; idx is -1 where that update was void, see stats()["status"])."""
+        n = self.batch
+        updates = int(updates)
+        u = None
+        if uniforms is not None:
+            u = torch.as_tensor(uniforms, dtype=torch.float64).to(self.device).contiguous()
+            if u.numel() != max(updates, 0) * n:
+                raise ValueError(f"DQNLearner.update_from: uniforms must hold updates x batch = {updates} x {n} values")
+        self.desc.isw = self.isw.data_ptr()
+        self.desc.batch = n
+        rp = _lib.DqnReplay(trans=replay.trans.data_ptr(), prios=replay.prios.data_ptr(), per_work=replay.work.data_ptr(),
+                            idx=self.idx.data_ptr(), u=u.data_ptr() if u is not None else None, cap=replay.cap,
+                            size=replay.size, alpha=replay.alpha, beta_start=float(beta_start),
+                            beta_frames=int(beta_frames), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+        check(self.lib.pm_dqn_replay_update(ctypes.byref(self.desc), ctypes.byref(rp), updates, stream_ptr(stream)),
+              "pm_dqn_replay_update")
+        replay.max_prio_stale = True
+        return self.idx[:n], self.td[:n]
 
     def grads(self, *batch, isw=None, stream=None):
         if batch:
@@ -169,3 +199,37 @@ class DQNLearner:
 
     def set_train_steps(self, steps):
         self._set_stats(steps=int(steps))
+
+
+class ReplayTrainer:
+    """Collect-and-train over the whole QNet (or its heads) at device speed: run(iterations) alternates
+
+        rollout.run(collect_steps, replay=replay, sync=False)   # pm_rollout_push: n * collect_steps transitions
+        learner.update_from(replay, updates)                    # pm_dqn_replay_update
+        rollout.set_paramsB(learner.params)                     # the next rollout plays the trained modelB
+
+    and returns the accumulated rollout stats (pongmi.rollout.STATS_PUSH) as host ints. Per iteration the
+    host reads 4 bytes (DeviceReplay.push_prio's max(prios), the priority memory.push stores, :57) and
+    nothing else; the stats are summed on the device and read once at the end."""
+
+    def __init__(self, env, wA, learner, replay, *, collect_steps, updates, epsilon=0.02, seed_net=0, beta_start=0.4,
+                 beta_frames=100000, seed=0):
+        from .rollout import SelfPlayRollout
+        self.learner, self.replay = learner, replay
+        self.collect_steps, self.updates = int(collect_steps), int(updates)
+        if self.collect_steps < 1 or self.updates < 1:
+            raise ValueError("ReplayTrainer: collect_steps and updates must be >= 1")
+        if self.collect_steps * env.n > replay.cap:
+            raise ValueError(f"ReplayTrainer: collect_steps * arenas = {self.collect_steps * env.n} > cap {replay.cap}")
+        self.beta_start, self.beta_frames, self.seed = float(beta_start), int(beta_frames), int(seed)
+        self.rollout = SelfPlayRollout(env, wA, learner.params, epsilon=epsilon, seed_net=seed_net)
+
+    def run(self, iterations):
+        from .rollout import STATS_PUSH
+        total = torch.zeros_like(self.rollout.stats)
+        for _ in range(int(iterations)):
+            total += self.rollout.run(self.collect_steps, replay=self.replay, sync=False)
+            self.learner.update_from(self.replay, self.updates, beta_start=self.beta_start,
+                                     beta_frames=self.beta_frames, seed=self.seed)
+            self.rollout.set_paramsB(self.learner.params)
+        return dict(zip(STATS_PUSH, (int(v) for v in total.cpu().tolist())))

@@ -50,7 +50,9 @@ class DeviceReplay:
     tree of pm_per_sample (`work`), which every collecting launch leaves current. pos / size mirror
     memory.pos / len(memory.buffer); max_prio is the priority the next push stores (max(prios), 1.0
     while empty, :57) — pushes never change it, so it is tracked here; call refresh() after
-    changing prios by other means (it also rebuilds the sum tree)."""
+    changing prios by other means (it also rebuilds the sum tree). push() adds the caller's own
+    transitions (pm_replay_push); DQNLearner.update_from trains from the ring and keeps the tree
+    current itself (it marks max_prio stale, and the next push_prio() re-reads it)."""
 
     def __init__(self, cap, device, alpha=0.6):
         self.cap = int(cap)
@@ -64,19 +66,53 @@ class DeviceReplay:
         self.pos = 0
         self.size = 0
         self.max_prio = 1.0
+        self.max_prio_stale = False  # set by DQNLearner.update_from: prios changed on the device
 
     def push_prio(self):
+        """The priority the next push stores. After DQNLearner.update_from changed prios on the device the
+        tracked maximum is stale: it is read back once here (self.prios.max(), :57 — a 4-byte host sync)."""
+        if self.max_prio_stale and self.size > 0:
+            self.max_prio = float(self.prios[:self.size].max())
+        self.max_prio_stale = False
         return self.max_prio if self.size > 0 else 1.0
 
     def advance(self, pushed):
         self.pos = (self.pos + pushed) % self.cap
         self.size = min(self.cap, self.size + pushed)
 
+    def push(self, s, a, r, ns, done, stream=None):
+        """memory.push (:56-63) of n <= cap transitions of the caller's (tensors or arrays of any device /
+        dtype: s, ns [n, 7]; a in 0..2, r, done [n]) at pos with push_prio() as their priority
+        (pm_replay_push); the sum tree stays current. Actions are checked where the host sees them (inputs
+        not on the device)."""
+        dev = self.trans.device
+        s = torch.as_tensor(s)
+        n = int(s.reshape(-1, 7).shape[0])
+        if not 1 <= n <= self.cap:
+            raise ValueError(f"DeviceReplay.push: {n} transitions (1..cap={self.cap})")
+        a = torch.as_tensor(a).reshape(n)
+        if not a.is_cuda and n and (int(a.min()) < 0 or int(a.max()) > 2):
+            raise ValueError("DeviceReplay.push: actions must be 0, 1 or 2")
+        f32 = dict(device=dev, dtype=torch.float32)
+        s = s.reshape(n, 7).to(**f32).contiguous()
+        ns = torch.as_tensor(ns).reshape(n, 7).to(**f32).contiguous()
+        r = torch.as_tensor(r).reshape(n).to(**f32).contiguous()
+        a = a.to(device=dev, dtype=torch.int32).contiguous()
+        done = torch.as_tensor(done).reshape(n).to(device=dev, dtype=torch.uint8).contiguous()
+        prio = self.push_prio()
+        check(_lib.load().pm_replay_push(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos, self.alpha,
+                                         prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done), n, stream_ptr(stream)),
+              "pm_replay_push")
+        if self.size == 0:
+            self.max_prio = 1.0
+        self.advance(n)
+
     def refresh(self):
         """After the host changed prios: rebuild the sum tree (pm_per_build) and the tracked max."""
         check(_lib.load().pm_per_build(ptr(self.prios), self.cap, self.alpha, ptr(self.work), stream_ptr()),
               "pm_per_build")
         self.max_prio = float(self.prios[:self.size].max()) if self.size else 1.0
+        self.max_prio_stale = False
 
     def leaves(self):
         """The PER leaves (prio^alpha, f32 [cap]) inside the tree workspace."""
