@@ -7,7 +7,8 @@
 // exactly the B-operand fragment the next layer needs for a k-step covering those two rows — so
 // layer 1 -> ReLU -> layer 2 runs on registers with no LDS round trip or lane shuffle. Per tile:
 // 8 MFMAs (7->64, K padded to 8) + 64 MFMAs (64->64); the 4 head outputs (V, A0..2) are 128 VALU
-// FMAs per lane + one cross-half add, overlapped with the next tile's MFMAs.
+// FMAs per lane + one cross-half add (tile_heads), or one chain of 32 v_mfma_f32_4x4x1_f32 with the
+// same bits where a block's waves run them at once (tile_heads_mfma: run_tiles, k_learn's feature blocks).
 //
 // Weights are stored pre-arranged in "fragment order" (PM_QNET_NW block, after the plain part) so a
 // wave reads each operand with one conflict-free ds_read_b128 per 4 MFMAs after a block stages the
@@ -18,6 +19,7 @@
 namespace pm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4v16 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;  // LDS destination of global_load_lds
 
 constexpr int PLAIN = 4936;  // plain effective weights (4932) padded to 16 B
@@ -373,20 +375,97 @@ __device__ __forceinline__ void heads_half(const float* hf, const f32x16& c2, in
 
 // tile_heads' tail after the chains (heads_half over both layer-2 tiles): the cross-half add, the
 // biases and Q = V + (A - mean(A)).
-__device__ __forceinline__ void heads_finish(const float (&acc)[4], const float* hf, float (&q)[3]) {
+// (bh: the four biases, hf + 256)
+__device__ __forceinline__ void heads_finish_b(const float (&acc)[4], const float* bh, float (&q)[3]) {
     float v = acc[0], a0 = acc[1], a1 = acc[2], a2 = acc[3];
     v += __shfl_xor(v, 32);
     a0 += __shfl_xor(a0, 32);
     a1 += __shfl_xor(a1, 32);
     a2 += __shfl_xor(a2, 32);
-    v += hf[256];
-    a0 += hf[257];
-    a1 += hf[258];
-    a2 += hf[259];
+    v += bh[0];
+    a0 += bh[1];
+    a1 += bh[2];
+    a2 += bh[3];
     const float mean = ((a0 + a1) + a2) / 3.0f;  // A.mean(dim=1)
     q[0] = v + (a0 - mean);
     q[1] = v + (a1 - mean);
     q[2] = v + (a2 - mean);
+}
+__device__ __forceinline__ void heads_finish(const float (&acc)[4], const float* hf, float (&q)[3]) {
+    heads_finish_b(acc, hf + 256, q);
+}
+
+// ----------------------------------------------------------------------------- heads on the matrix cores
+// tile_heads' four fmaf chains of a 32-row tile as one chain of 32 v_mfma_f32_4x4x1_16b_f32 (16 blocks of
+// 4 lanes, D[i][j] += A[i] * B[j] per block; a chain of them is the k-ordered fmaf chain bit for bit,
+// tools/mfma4_probe.hip): lane l supplies its own ReLU(c2) value as B and the weight of output l & 3 (V,
+// A0, A1, A2) as A. The four lanes of a block share the lane half and the accumulator register, so they
+// stand at the same chain position 16 t + r, and every lane ends with its column's four half sums in
+// tile_heads' order. A tile costs 32 MFMAs of 8 cycles and eight 16-byte LDS reads where the VALU form
+// costs 128 FMAs and 32 reads (1 KB per wave each: what bounds a CU whose 16 waves run their heads at
+// once).
+//
+// The A operands, by output: the weight of output j at chain position q of half h is float
+// (4 h + j) * kOpwStride + q (F_H element ((32 h + q) * 4 + j)); the row stride of 36 floats puts the
+// eight rows a wave reads at once on different banks.
+constexpr int kOpwStride = 36;
+constexpr int kOpwFloats = 8 * kOpwStride;
+// where F_H element k ([h 2][q 32][c 4]) goes
+__device__ __forceinline__ int opw_slot(int k) { return (4 * (k >> 7) + (k & 3)) * kOpwStride + ((k >> 2) & 31); }
+
+__device__ __forceinline__ const float4* opw_row(const float* opw, int lane) {
+    return reinterpret_cast<const float4*>(opw + (4 * (lane >> 5) + (lane & 3)) * kOpwStride);
+}
+
+// heads_half on the matrix cores: the chain over layer-2 tile t (positions 16 t .. 16 t + 15), from acc.
+__device__ __forceinline__ void heads_half_mfma(const float* opw, const f32x16& c2, int lane, int t, f32x4v16& acc) {
+    const float4* aw = opw_row(opw, lane) + 4 * t;
+    float4 w = aw[0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float4 wn = aw[(k + 1) & 3];
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.x, relu(c2[4 * k + 0]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.y, relu(c2[4 * k + 1]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.z, relu(c2[4 * k + 2]), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_4x4x1f32(w.w, relu(c2[4 * k + 3]), acc, 0, 0, 0);
+        w = wn;
+    }
+}
+__device__ __forceinline__ void heads_finish_mfma(const f32x4v16& acc, const float* bh, float (&q)[3]) {
+    const float a[4] = {acc[0], acc[1], acc[2], acc[3]};
+    heads_finish_b(a, bh, q);
+}
+// tile_heads: the same bits. opw: the A operands above; bh: the four biases.
+__device__ __forceinline__ void tile_heads_mfma(const float* opw, const float* bh, const f32x16 (&c2)[2], int lane,
+                                                float (&q)[3]) {
+    f32x4v16 acc = {0.f, 0.f, 0.f, 0.f};
+    heads_half_mfma(opw, c2[0], lane, 0, acc);
+    heads_half_mfma(opw, c2[1], lane, 1, acc);
+    heads_finish_mfma(acc, bh, q);
+}
+// Two tiles' chains interleaved: one sweep of the A operands feeds both, and each chain's MFMA issues
+// in the other's dependent latency.
+__device__ __forceinline__ void tile_heads_mfma2(const float* opw, const float* bh, const f32x16 (&ca)[2],
+                                                 const f32x16 (&cb)[2], int lane, float (&qa)[3], float (&qb)[3]) {
+    const float4* aw = opw_row(opw, lane);
+    f32x4v16 xa = {0.f, 0.f, 0.f, 0.f}, xb = {0.f, 0.f, 0.f, 0.f};
+    float4 w = aw[0];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float4 wn = aw[(k + 1) & 7];
+        const int t = k >> 2, r = 4 * (k & 3);
+        xa = __builtin_amdgcn_mfma_f32_4x4x1f32(w.x, relu(ca[t][r + 0]), xa, 0, 0, 0);
+        xb = __builtin_amdgcn_mfma_f32_4x4x1f32(w.x, relu(cb[t][r + 0]), xb, 0, 0, 0);
+        xa = __builtin_amdgcn_mfma_f32_4x4x1f32(w.y, relu(ca[t][r + 1]), xa, 0, 0, 0);
+        xb = __builtin_amdgcn_mfma_f32_4x4x1f32(w.y, relu(cb[t][r + 1]), xb, 0, 0, 0);
+        xa = __builtin_amdgcn_mfma_f32_4x4x1f32(w.z, relu(ca[t][r + 2]), xa, 0, 0, 0);
+        xb = __builtin_amdgcn_mfma_f32_4x4x1f32(w.z, relu(cb[t][r + 2]), xb, 0, 0, 0);
+        xa = __builtin_amdgcn_mfma_f32_4x4x1f32(w.w, relu(ca[t][r + 3]), xa, 0, 0, 0);
+        xb = __builtin_amdgcn_mfma_f32_4x4x1f32(w.w, relu(cb[t][r + 3]), xb, 0, 0, 0);
+        w = wn;
+    }
+    heads_finish_mfma(xa, bh, qa);
+    heads_finish_mfma(xb, bh, qb);
 }
 
 // ----------------------------------------------------------------------------- 16-column tiles
@@ -408,8 +487,6 @@ __device__ __forceinline__ int head_pos(int u) {
     const int t = u >> 5, v = u & 31;
     return 16 * t + (v & 3) + 4 * (v >> 3);
 }
-
-typedef float f32x4v16 __attribute__((ext_vector_type(4)));
 
 // Head weights (F_H order, 260 floats) by output: opw[set][h][j][q] = weight of output j (V, A0, A1,
 // A2) at chain position q of half h, the A operands of the heads' v_mfma_f32_4x4x1_f32 chain (one wave).
@@ -448,9 +525,10 @@ struct TilePre {
 };
 
 // QNet forward + action for `count` arenas listed in LDS `list` (arena indices), weights staged in
-// LDS `lw`. Each wave takes tiles wave, wave + nwaves, ... Wave-uniform control flow throughout.
-__device__ __forceinline__ void run_tiles(const float* lw, const float* __restrict__ obs, const int* list, int count,
-                                          const TileOut& out, const TilePre pre) {
+// LDS `lw`, the heads by output in `opw` (tile_heads_mfma). Each wave takes tiles wave, wave + nwaves, ...
+// Wave-uniform control flow throughout.
+__device__ __forceinline__ void run_tiles(const float* lw, const float* opw, const float* __restrict__ obs,
+                                          const int* list, int count, const TileOut& out, const TilePre pre) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int h = lane >> 5, col = lane & 31;
     const int ntiles = (count + 31) >> 5;
@@ -487,7 +565,7 @@ __device__ __forceinline__ void run_tiles(const float* lw, const float* __restri
         if (tl == wave) PM_BLK(6);
 #endif
         float q[3];
-        tile_heads(lw + F_H, c2, lane, q);
+        tile_heads_mfma(opw, lw + F_BH, c2, lane, q);
 #ifdef PM_DIAG
         if (tl == wave) PM_BLK(7);
 #endif
@@ -532,6 +610,7 @@ template <int LIST>
 struct ActSharedT {
     static constexpr int kList = LIST;
     float lw[kLwFloats];  // fragment image, padded to whole 1 KB wave chunks
+    float opw[kOpwFloats];  // its heads by output (tile_heads_mfma's A operands)
     int list[LIST];
     int count;
     int wtot[16];  // one per wave: up to 1024-thread blocks (k_learn's side-A act blocks)
@@ -573,6 +652,8 @@ __device__ __forceinline__ void act_block(Sh& sh, const ActGrid& g, const float*
     // VALU/LDS work loses arbitration to co-resident waves' f32 MFMA streams), the tiles at normal.
     __builtin_amdgcn_s_setprio(2);
     stage_frags_lds(w, sh.lw, b);
+    // the heads once more, as a plain load in the same round trip: they go to LDS by output below
+    const float hv = threadIdx.x < 256 ? w[PLAIN + F_H + threadIdx.x] : 0.f;
     // opponent rows: from the env kernel's per-block lists when the chunk is whole 256-arena blocks
     const bool lists = compact && opp_list != nullptr && (lo & 255) == 0 && (((hi - lo) & 255) == 0 || hi == g.n);
     int ids[16];
@@ -616,10 +697,11 @@ __device__ __forceinline__ void act_block(Sh& sh, const ActGrid& g, const float*
             tile_inputs(obs + (size_t)(lo + min(wave * 32 + (lane & 31), cnt - 1)) * 7, lane >> 5, pre.xs);
         }
     }
+    if (threadIdx.x < 256) sh.opw[opw_slot(threadIdx.x)] = hv;
     __syncthreads();
     PM_BLK(1);
     __builtin_amdgcn_s_setprio(0);
-    run_tiles(sh.lw, obs, sh.list, sh.count, out, pre);
+    run_tiles(sh.lw, sh.opw, obs, sh.list, sh.count, out, pre);
 }
 
 // modelB's hidden features for the NEXT vector step, computed ahead of the update (the features

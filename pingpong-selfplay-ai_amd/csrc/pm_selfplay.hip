@@ -170,7 +170,9 @@ __device__ __forceinline__ void gh_publish(const pm_selfplay& sp, int k, uint32_
 // the hand-off described above. Block-wide, every barrier block-uniform.
 struct FeatAheadSmem {
     float lw[kLwFloats];  // modelB's acting fragment image (the feature layers)
-    float hf[264];        // the next step's acting heads in F_H | F_BH fragment order, from the granules
+    // the next step's acting heads from the granules: by output (pm_mfma.h opw_slot: tile_heads_mfma's A
+    // operands), then the four biases
+    __attribute__((aligned(16))) float hf[kOpwFloats + 8];
     int ok;               // every granule arrived
 };
 __device__ __forceinline__ void feat_tiles_ahead(const pm_selfplay& sp, FeatAheadSmem& sm, int t0, int t1, bool force_timeout) {
@@ -202,28 +204,33 @@ __device__ __forceinline__ void feat_tiles_ahead(const pm_selfplay& sp, FeatAhea
             if ((uint32_t)(g >> 32) == tag) { got = true; break; }
             __builtin_amdgcn_s_sleep(2);
         }
-        if (got) sm.hf[t] = __uint_as_float((uint32_t)g);
+        if (got) sm.hf[t < 256 ? opw_slot(t) : kOpwFloats + t - 256] = __uint_as_float((uint32_t)g);
         else sm.ok = 0;
     }
     __syncthreads();
     PM_STAMP_MAX_NB(69);
     const bool ok = sm.ok != 0;  // block-uniform
-    // (one sweep of the head weights per tile: the sweeps' LDS reads, 1 KB per wave and step, bound this
-    // tail, ~18 tiles x 32 steps per CU; a two-tile sweep halves them but spilled at this kernel's
-    // 128-register cap)
+    // the heads on the matrix cores (tile_heads_mfma: the VALU sweeps' LDS reads, 1 KB per wave and step
+    // over ~18 tiles x 32 steps per CU, bound this tail, which ends the launch); a wave with two tiles
+    // runs both chains in one sweep of the operands
+    int a[2] = {PM_GB_NONE, PM_GB_NONE};
+    if (ok) {
+        float q0[3], q1[3];
+        if (has[1]) {  // wave-uniform; has[1] implies has[0]
+            tile_heads_mfma2(sm.hf, sm.hf + kOpwFloats, c2[0], c2[1], lane, q0, q1);
+            a[0] = argmax3(q0);
+            a[1] = argmax3(q1);
+        } else if (has[0]) {
+            tile_heads_mfma(sm.hf, sm.hf + kOpwFloats, c2[0], lane, q0);
+            a[0] = argmax3(q0);
+        }
+    }
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (!has[k]) continue;  // wave-uniform
         const int arena = tl[k] * 32 + (lane & 31);
-        int a = PM_GB_NONE;
-        if (ok) {
-            float q[3];
-            tile_heads(sm.hf, c2[k], lane, q);
-            a = argmax3(q);
-        } else {
-            feat_store(sp.featB, tl[k], lane, c2[k]);
-        }
-        if (lane < 32 && arena < sp.n) sp.gB[arena] = (int8_t)a;
+        if (!ok) feat_store(sp.featB, tl[k], lane, c2[k]);
+        if (lane < 32 && arena < sp.n) sp.gB[arena] = (int8_t)a[k];
     }
 }
 
@@ -928,6 +935,34 @@ __device__ __forceinline__ void adam_one(const pm_selfplay& sp, ApplySmem& sm, i
     sm.hp[k] = p;
     sm.m[k] = m;  // k_learn_multi runs the next update from LDS
     sm.v[k] = v;
+}
+// adam_one on two parameters, every load first: the two chains (a square root and two divisions each) run
+// side by side instead of the second's loads waiting behind the first's LDS stores
+__device__ __forceinline__ void adam_two(const pm_selfplay& sp, ApplySmem& sm, int k0, float g0s, int k1, float g1s) {
+    const float step_size = sm.ak[0], bc2s = sm.ak[1];
+    const float g0 = g0s / (float)sp.world, g1 = g1s / (float)sp.world;
+    float m0 = sm.m[k0], v0 = sm.v[k0], p0 = sm.hp[k0];
+    float m1 = sm.m[k1], v1 = sm.v[k1], p1 = sm.hp[k1];
+    m0 = m0 + (float)(1.0 - sp.beta1) * (g0 - m0);
+    m1 = m1 + (float)(1.0 - sp.beta1) * (g1 - m1);
+    v0 = v0 * (float)sp.beta2 + (float)(1.0 - sp.beta2) * g0 * g0;
+    v1 = v1 * (float)sp.beta2 + (float)(1.0 - sp.beta2) * g1 * g1;
+    const float d0 = sqrtf(v0) / bc2s + (float)sp.adam_eps;
+    const float d1 = sqrtf(v1) / bc2s + (float)sp.adam_eps;
+    p0 = p0 - step_size * (m0 / d0);
+    p1 = p1 - step_size * (m1 / d1);
+    sm.hp[k0] = p0;
+    sm.hp[k1] = p1;
+    sp.paramsB[PM_QNET_HEAD_OFF + k0] = p0;
+    sp.adam_m[k0] = m0;
+    sp.adam_v[k0] = v0;
+    sp.paramsB[PM_QNET_HEAD_OFF + k1] = p1;
+    sp.adam_m[k1] = m1;
+    sp.adam_v[k1] = v1;
+    sm.m[k0] = m0;
+    sm.v[k0] = v0;
+    sm.m[k1] = m1;
+    sm.v[k1] = v1;
 }
 __device__ __forceinline__ void apply_adam(const pm_selfplay& sp, ApplySmem& sm) {
     const int t = threadIdx.x, nt = blockDim.x;
@@ -1860,8 +1895,7 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
             gs[kmu] = g;
             gs[ksg] = gsg;
             if (sp.fuse_apply) {  // the optimizer step on the two parameters this thread owns
-                adam_one(sp, sm.ap, kmu, g);
-                adam_one(sp, sm.ap, ksg, gsg);
+                adam_two(sp, sm.ap, kmu, g, ksg, gsg);
             }
         } else if (t < 260) {  // dL/db_mu = sum_j coef_j
             const int k = t - 256;
@@ -1874,8 +1908,7 @@ __global__ __launch_bounds__(kLearn) void k_learn(const pm_selfplay sp, int chun
             gs[kmu] = g;
             gs[ksg] = gsg;
             if (sp.fuse_apply) {
-                adam_one(sp, sm.ap, kmu, g);
-                adam_one(sp, sm.ap, ksg, gsg);
+                adam_two(sp, sm.ap, kmu, g, ksg, gsg);
             }
         }
         // actions ahead: thread t < 260 owns both parameters (mu, sigma) of the acting head value t,
