@@ -193,6 +193,9 @@ def _check_update(orc, L, c, snap, kind, adam=None, *, u=0, mode=None, sync=3, g
       "multi"      update `u` of a U > 1 step through learn_ex(mode) / apply_ex(mode): PER draw, noise,
                    head gradients, priority scatter, episodes counted by update 0 only; then Adam,
                    train_steps / frame_idx, target sync, epsilon (decays with update 0 only).
+    The counters may start anywhere (tests/test_gpu_selfplay_late.py injects late ones): train_steps and
+    frame_idx must each advance by one, `adam["t"]` counts with train_steps, the target syncs when
+    (train_steps + 1) % sync == 0, and beta follows the learner's beta_frames.
     Tolerances: gradients rtol 2e-4 / atol `grad_atol`, loss rtol 1e-4, priorities rtol 2e-5 /
     atol 3e-5, Adam rtol 1e-5 / atol 1e-7. `loss_figs` (a list): the device's and the reference's own
     float32 (_dqn_loss_f32) relative loss errors against float64 are appended and printed;
@@ -210,7 +213,7 @@ def _check_update(orc, L, c, snap, kind, adam=None, *, u=0, mode=None, sync=3, g
     if kind == "single":
         assert size >= L.batch
     frame = c["frame_idx"] + 1
-    beta = min(1.0, 0.4 + frame * 0.6 / 100000)
+    beta = min(1.0, 0.4 + frame * 0.6 / L.hparams["beta_frames"])
     r = orc.philox64(np.arange(L.batch), orc.TAG_PER, np.full(L.batch, frame, np.uint64), sp.seed_env)
     idx = L.idx.cpu().numpy()
     w = _check_per(orc, snap["prios"], size, L.cap, beta, orc.u53(r[0], r[1]), idx, L.isw.cpu().numpy())
@@ -260,13 +263,15 @@ def _check_update(orc, L, c, snap, kind, adam=None, *, u=0, mode=None, sync=3, g
                                                 2.5e-4)
     np.testing.assert_allclose(L.paramsB.cpu().numpy()[4672:5192], p_ref, rtol=1e-5, atol=1e-7)
     after = L.counters()
-    assert after["train_steps"] == updates and after["frame_idx"] == updates
-    if updates % sync == 0:
+    # both counters advance by one from wherever the update found them, and Adam's step count with them
+    assert after["train_steps"] == c["train_steps"] + 1 == updates and after["frame_idx"] == c["frame_idx"] + 1
+    if (c["train_steps"] + 1) % sync == 0:
         assert np.array_equal(L.paramsT.cpu().numpy()[:5192], L.paramsB.cpu().numpy()[:5192])
     elif kind == "single":
         assert np.array_equal(L.paramsT.cpu().numpy(), snap["paramsT"])
     if u == 0:
-        assert np.isclose(after["epsilon"], max(0.02, c["epsilon"] * 0.995 ** grad[520]), rtol=1e-12)
+        # float(): a float32 exponent would make numpy evaluate the power in float32
+        assert np.isclose(after["epsilon"], max(0.02, c["epsilon"] * 0.995 ** float(grad[520])), rtol=1e-12)
     else:
         assert after["epsilon"] == c["epsilon"]
     if kind == "single":
