@@ -14,7 +14,10 @@
 #include "pongmi.h"
 
 #ifdef PM_DIAG
-// TU-local (no -fgpu-rdc): only pm_selfplay.hip stamps, and it exports the reader.
+// TU-local (no -fgpu-rdc): every unit whose kernels stamp has its own copy of pm_diag_buf and
+// pm_diag_blk and exports the readers of that copy (pm_sp_learn.hip: pm_diag_read / pm_diag_clear /
+// pm_diag_read_blk_learn; pm_sp_rollout.hip: pm_diag_read_sp_rollout / pm_diag_clear_sp_rollout /
+// pm_diag_read_blk; pm_drqn.hip: pm_diag_read_drqn / pm_diag_clear_drqn).
 static __device__ unsigned long long pm_diag_buf[256];
 #define PM_STAMP(slot)                                                                 \
     do {                                                                               \

@@ -60,5 +60,6 @@ inline void pm_launch(int timer, F kernel, dim3 grid, dim3 block, hipStream_t st
 
 // ---------------------------------------------------------------- diagnostic stamps (PM_DIAG builds only)
 // libpongmi_diag.so is built with -DPM_DIAG: thread 0 of block 0 records s_memrealtime (100 MHz)
-// at named phase boundaries into pm_diag_buf; pm_diag_read copies them out. The product library
-// compiles every stamp to nothing.
+// at named phase boundaries into its translation unit's pm_diag_buf (pm_dev.h); the unit's reader
+// (pm_diag_read for the self-play learner unit, pm_diag_read_sp_rollout for its rollout unit,
+// pm_diag_read_drqn) copies them out. The product library compiles every stamp to nothing.

@@ -1,4 +1,4 @@
-// PER pieces shared between pm_replay.hip and pm_selfplay.hip.
+// PER pieces shared between pm_replay.hip and the self-play learner's units (pm_sp_rollout.hip, pm_sp_learn.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

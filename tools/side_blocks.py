@@ -27,7 +27,7 @@ def main():
     lib = _lib.load()
     lib.pm_diag_read_side.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     lib.pm_diag_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]
-    lib.pm_diag_read_blk.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    lib.pm_diag_read_blk_learn.argtypes = [ctypes.POINTER(ctypes.c_uint64)]  # the learner unit's block timeline
     n = 65536
     sdB, sdA = bench.synthetic_qnet(1), bench.synthetic_qnet(2)
     pool = [bench.synthetic_qnet(100 + k) for k in range(8)]
@@ -35,7 +35,7 @@ def main():
     for _ in range(40):
         L.step()
     torch.cuda.synchronize()
-    # the host's learn_grid (pm_selfplay.hip) on a 256-CU device
+    # the host's learn_grid (pm_sp_learn.hip) on a 256-CU device
     ntiles = (n + 31) // 32
 
     def chunk(p):
@@ -55,7 +55,7 @@ def main():
         torch.cuda.synchronize()
         lib.pm_diag_read_side(side)
         lib.pm_diag_read(buf, 256)
-        lib.pm_diag_read_blk(blk)  # act_block's PM_BLK stamps of the side-A blocks (grid blocks 2 ..)
+        lib.pm_diag_read_blk_learn(blk)  # act_block's PM_BLK stamps of the side-A blocks (grid blocks 2 ..)
         b = np.array(blk[:], dtype=np.int64).reshape(8, 4096)[:, 2:2 + nact]
         a = np.array(side[:], dtype=np.int64).reshape(4, 1024)[:, :nact + nfeat]
         t0 = int(buf[0])  # learner start

@@ -3,10 +3,12 @@
     make -C pingpong-selfplay-ai_amd/csrc diag && python tools/stamps.py [--steps 20]
 
 Thread 0 of block 0 of each learner kernel records s_memrealtime (100 MHz) at phase boundaries
-(PM_STAMP in pm_selfplay.hip); this prints the median time of every stamp relative to the start of
-the step's first kernel (k_actenv's first env block in the fused step, k_act_sp's first act block in
-the plain one), i.e. the critical path through act + env (+ PER sample blocks) -> learn.
-Diagnostic only (libpongmi_diag.so, never the product library).
+(PM_STAMP in pm_sp_learn.hip and pm_sp_rollout.hip); this prints the median time of every stamp
+relative to the start of the step's first kernel (k_actenv's first env block in the fused step,
+k_act_sp's first act block in the plain one), i.e. the critical path through act + env (+ PER sample
+blocks) -> learn. The stamp buffer is per translation unit: slots 64, 65, 70 and 72 (ROLLOUT_SLOTS) come
+from the rollout unit's copy (pm_diag_read_sp_rollout), every other slot from the learner unit's
+(pm_diag_read). Diagnostic only (libpongmi_diag.so, never the product library).
 """
 import argparse
 import ctypes
@@ -41,6 +43,7 @@ NAMES = {
     69: "feature blocks: heads in LDS (max)",
     5: "learn tree level1", 6: "learn tree level2", 20: "apply adam", 21: "apply derive", 7: "learn end",
 }
+ROLLOUT_SLOTS = [64, 65, 70, 72]  # stamped by k_act_sp / k_env / k_actenv
 
 
 def main():
@@ -55,6 +58,7 @@ def main():
     from pongmi.selfplay import SelfPlayLearner
     lib = _lib.load()
     lib.pm_diag_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]
+    lib.pm_diag_read_sp_rollout.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]
     sdB, sdA = bench.synthetic_qnet(1), bench.synthetic_qnet(2)
     pool = [bench.synthetic_qnet(100 + k) for k in range(8)]
     L = SelfPlayLearner(bench.ENV_KW, args.arenas, sdB, sdA, pool, batch=256, memory_size=1_000_000,
@@ -62,14 +66,17 @@ def main():
     for _ in range(args.warmup):
         L.step()
     torch.cuda.synchronize()
-    buf = (ctypes.c_uint64 * 256)()
+    buf, rbuf = (ctypes.c_uint64 * 256)(), (ctypes.c_uint64 * 256)()
     rows = []
     for _ in range(args.steps):
         lib.pm_diag_clear()
+        lib.pm_diag_clear_sp_rollout()
         L.step()
         torch.cuda.synchronize()
         lib.pm_diag_read(buf, 256)
+        lib.pm_diag_read_sp_rollout(rbuf, 256)
         v = np.array(buf[:], dtype=np.int64)
+        v[ROLLOUT_SLOTS] = np.array(rbuf[:], dtype=np.int64)[ROLLOUT_SLOTS]
         rows.append(v)
     a = np.stack(rows)
     base = a[:, 70:71] if (a[:, 70] != 0).all() else a[:, 72:73]
