@@ -443,6 +443,45 @@ int pm_dqn_apply(const pm_dqn* d, void* stream);
 /* pm_dqn_grads then pm_dqn_apply on one replica, as one launch (the same arithmetic: bit-identical). */
 int pm_dqn_update(const pm_dqn* d, void* stream);
 
+/* Loss and clip options of the stand-alone learner (additive to ABI 27, as pm_dqn_replay: a size function
+ * of its own, pm_sizeof unchanged). The _opt entry points run the same update as the plain ones with two
+ * things a caller may choose, both torch's:
+ *   loss      PM_DQN_LOSS_HUBER: with diff = q - t, ad = |diff|, w = isw or 1, beta = (float)huber_beta the
+ *             row's loss term is w * (ad < beta ? 0.5f * diff * diff / beta : ad - 0.5f * beta) and
+ *             dL/dq = (w / batch) * (ad < beta ? diff / beta : sign(diff)):
+ *             (isw * F.smooth_l1_loss(q, t, reduction='none', beta=beta)).mean(). For beta = 1 the
+ *             quadratic zone is HALF the squared loss: gradient diff, not PM_DQN_LOSS_SQUARED's 2 diff.
+ *             td stays |q - t| (priorities do not depend on the loss); stats, q and everything behind
+ *             dL/dq are formed as before. A row with diff == 0 contributes no gradient.
+ *   max_norm  > 0: torch.nn.utils.clip_grad_norm_(trained parameters, max_norm) in the apply step, after
+ *             gk = grad / count and before Adam, so replicas that all-reduce clip on the norm of the
+ *             averaged gradient and every rank derives the same coefficient. norm = sqrt(sum gk^2) over
+ *             the trained slots only ([PM_QNET_HEAD_OFF, PM_DQN_NPARAM) in heads-only mode, the sigma
+ *             gradients included; [0, PM_DQN_NPARAM) with train_features), coef = min(1, (float)(max_norm /
+ *             ((double)norm + 1e-6))), Adam consumes gk * coef. grad keeps the UNCLIPPED gradient, in its
+ *             usual layout. The sum of squares has one fixed order and no atomic: per thread in fp64 in
+ *             slot order, a wave sum, the 16 wave sums added in wave order. A clip that does not bite
+ *             (coef == 1.0f) leaves every bit as without one.
+ *   norm      nullable device float: the total norm before the clip of the last apply, written whenever it
+ *             is non-null, clip or no clip; untouched where the apply step does nothing (count 0, or a
+ *             void update of pm_dqn_replay_update_opt).
+ * A null opt means the defaults: squared loss, no clip, no norm out; the results then equal the plain
+ * entry points' bit for bit. PM_E_ARG, before any launch: an unknown loss; huber_beta <= 0 or not finite
+ * with PM_DQN_LOSS_HUBER; max_norm < 0 or not finite; and whatever the plain entry point rejects. */
+#define PM_DQN_LOSS_SQUARED 0   /* mean(isw * (q - t)^2): the reference, train_iterative.py:158 */
+#define PM_DQN_LOSS_HUBER   1   /* mean(isw * smooth_l1(q - t, beta)) */
+typedef struct pm_dqn_opt {
+    int32_t loss;        /* PM_DQN_LOSS_* */
+    int32_t _pad;
+    double  huber_beta;  /* > 0, finite; read only with PM_DQN_LOSS_HUBER */
+    double  max_norm;    /* 0: no clip; > 0, finite: clip_grad_norm_(trained parameters, max_norm) */
+    float  *norm;        /* nullable, device [1]: total norm before the clip of the last apply */
+} pm_dqn_opt;
+size_t pm_dqn_opt_sizeof(void);
+int pm_dqn_grads_opt(const pm_dqn* d, const pm_dqn_opt* opt, void* stream);  /* reads loss / huber_beta */
+int pm_dqn_apply_opt(const pm_dqn* d, const pm_dqn_opt* opt, void* stream);  /* reads max_norm / norm */
+int pm_dqn_update_opt(const pm_dqn* d, const pm_dqn_opt* opt, void* stream);
+
 /* The same update drawn from a device replay (csrc/pm_dqn_replay.hip), `updates` times in one call, on the
  * stream, with no host synchronisation or copy. Per update: frame = d->stats->steps + 1 (read on the
  * device: frame_idx += 1 before sampling, :136), beta = min(1, beta_start + frame (1 - beta_start) /
@@ -472,6 +511,9 @@ typedef struct pm_dqn_replay {
 } pm_dqn_replay;
 size_t pm_dqn_replay_sizeof(void);
 int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates, void* stream);
+/* pm_dqn_replay_update with pm_dqn_update_opt as its update; a void update skips loss, clip and norm alike. */
+int pm_dqn_replay_update_opt(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, int32_t updates,
+                             void* stream);
 
 /* memory.push (:56-63) of n caller transitions, 0 < n <= cap, all device buffers: transition i goes to slot
  * (pos + i) mod cap as a PM_TRANS_F row, prios = prio (the caller's max(prios), 1 while empty), leaf =

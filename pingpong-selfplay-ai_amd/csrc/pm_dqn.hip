@@ -23,6 +23,14 @@
 //   Rows >= batch are never read; their operands are zeros.
 //   k_dqn_apply  grad / count, torch.optim.Adam over [4672, 5192) or all of [0, 5192), target sync, counters.
 //   k_dqn_update both bodies in one launch (pm_dqn_update), a barrier between them.
+//   k_*_opt      the same bodies with a pm_dqn_opt (pm_dqn_*_opt): phase 2 may form the Huber (smooth-L1) loss
+//     term and dL/dq instead of the squared ones, and the apply body may clip on the total norm of grad /
+//     count over the trained slots: per thread the squares in fp64 in slot order, a DPP wave sum, the 16
+//     wave sums through LDS under the barrier the body already has, added in wave order by every thread (no
+//     further barrier, no global round trip, no atomic). The bodies are templates; the plain kernels are
+//     their <false> instantiations and keep their device text (tools/kernel_text.py against the parent).
+#include <cmath>
+
 #include "pm_dev.h"
 #include "pm_host.h"
 #include "pm_mfma.h"
@@ -83,7 +91,9 @@ __device__ __forceinline__ void store_acc_rows(float* r, int row, bool valid, in
 }
 
 // Block-wide (kDqn threads). Returns with every store issued; the caller's barrier publishes them.
-__device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, DqnSmem& sm) {
+// kOpt: o.loss selects the row loss of phase 2; without it o is not read.
+template <bool kOpt>
+__device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, const pm_dqn_opt& o, DqnSmem& sm) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int col = lane & 31, h = lane >> 5;
     const int B = d.batch, ntiles = (B + 31) >> 5, nrows = ntiles * 32;
@@ -177,6 +187,11 @@ __device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, DqnSmem& sm) {
             d.td[t] = fabsf(diff);
             lterm = w * (diff * diff);
             gv = (w * (1.0f / (float)B)) * (2.0f * diff);  // mean, then iw *, then pow(2)'s 2 * diff
+            if (kOpt && o.loss == PM_DQN_LOSS_HUBER) {  // (iw * smooth_l1_loss(q, t, 'none', beta)).mean()
+                const float beta = (float)o.huber_beta, ad = fabsf(diff);
+                lterm = w * (ad < beta ? 0.5f * diff * diff / beta : ad - 0.5f * beta);
+                gv = (w * (1.0f / (float)B)) * (ad < beta ? diff / beta : (diff > 0.f ? 1.0f : -1.0f));
+            }
             gm = gv / 3.0f;                                // A.mean(dim=1)'s backward
         }
         const float g0 = gv, g1 = (a == 0 ? gv : 0.f) - gm, g2 = (a == 1 ? gv : 0.f) - gm, g3 = (a == 2 ? gv : 0.f) - gm;
@@ -332,7 +347,10 @@ __device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, DqnSmem& sm) {
 // grad / count -> torch.optim.Adam (single-tensor path, as k_adam's adam_one) -> target sync -> counters.
 // Every load is issued before the first store (the buffers may alias as far as the compiler knows, and a
 // load behind a store would wait for it: five round trips instead of one over the whole net). Block-wide.
-__device__ __forceinline__ void dqn_apply_body(const pm_dqn& d, float (&ak)[2]) {
+// kOpt: clip_grad_norm_ on grad / count over the trained slots (o.max_norm > 0) and the norm out (o.norm);
+// nsq: the 16 waves' sums of squares, published by the barrier that publishes ak.
+template <bool kOpt>
+__device__ __forceinline__ void dqn_apply_body(const pm_dqn& d, const pm_dqn_opt& o, float (&ak)[2], double* nsq) {
     const int t = threadIdx.x;
     const float count = d.grad[PM_DQN_NPARAM];
     if (!(count > 0.5f)) return;  // nobody contributed (block-uniform)
@@ -349,13 +367,37 @@ __device__ __forceinline__ void dqn_apply_body(const pm_dqn& d, float (&ak)[2]) 
         const int k = k0 + i * kDqn;
         if (k < PM_DQN_NPARAM) { g[i] = d.grad[k]; m[i] = d.adam_m[k]; v[i] = d.adam_v[k]; p[i] = d.params[k]; }
     }
+    if (kOpt) {  // full waves: the return above is block-uniform
+        double ss = 0.0;
+#pragma unroll
+        for (int i = 0; i < kPer; ++i)
+            if (k0 + i * kDqn < PM_DQN_NPARAM) {
+                const double gk = (double)(g[i] / count);
+                ss += gk * gk;
+            }
+        ss = wave_sum(ss);
+        if ((t & 63) == 0) nsq[t >> 6] = ss;
+    }
     __syncthreads();  // ak; also orders every thread's read of stats before thread 0's write below
     const float step_size = ak[0], bc2s = ak[1];
+    float coef = 1.0f;
+    if (kOpt) {  // every thread adds the same 16 sums in the same order: one coefficient, no second barrier
+        double ss = 0.0;
+#pragma unroll
+        for (int w = 0; w < kDqn / 64; ++w) ss += nsq[w];
+        const float norm = (float)sqrt(ss);
+        if (o.max_norm > 0.0) {
+            const float cc = (float)(o.max_norm / ((double)norm + 1e-6));  // clip_coef
+            coef = cc < 1.0f ? cc : 1.0f;                                  // clamp(clip_coef, max=1)
+        }
+        if (t == 0 && o.norm) *o.norm = norm;
+    }
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
         const int k = k0 + i * kDqn;
         if (k < PM_DQN_NPARAM) {
-            const float gk = g[i] / count;
+            float gk = g[i] / count;
+            if (kOpt) gk = gk * coef;
             float mk = m[i], vk = v[i];
             mk = mk + (float)(1.0 - d.beta1) * (gk - mk);                  // exp_avg.lerp_(grad, 1 - beta1)
             vk = vk * (float)d.beta2 + (float)(1.0 - d.beta2) * gk * gk;  // mul_(beta2).addcmul_(g, g, 1 - beta2)
@@ -383,12 +425,12 @@ __device__ __forceinline__ void dqn_apply_body(const pm_dqn& d, float (&ak)[2]) 
 
 __global__ __launch_bounds__(kDqn, 1) void k_dqn_grads(const pm_dqn d) {
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
-    dqn_grads_body(d, sm);
+    dqn_grads_body<false>(d, pm_dqn_opt{}, sm);
 }
 
 __global__ __launch_bounds__(kDqn, 1) void k_dqn_apply(const pm_dqn d) {
     __shared__ float ak[2];
-    dqn_apply_body(d, ak);
+    dqn_apply_body<false>(d, pm_dqn_opt{}, ak, nullptr);
 }
 
 // pm_dqn_update: both in one launch, the gradient handed over through grad (the same loads and the same
@@ -396,9 +438,9 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqn_apply(const pm_dqn d) {
 __global__ __launch_bounds__(kDqn, 1) void k_dqn_update(const pm_dqn d) {
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
     __shared__ float ak[2];
-    dqn_grads_body(d, sm);
+    dqn_grads_body<false>(d, pm_dqn_opt{}, sm);
     __syncthreads();
-    dqn_apply_body(d, ak);
+    dqn_apply_body<false>(d, pm_dqn_opt{}, ak, nullptr);
 }
 
 // pm_dqn_replay_update's middle launch: k_dqn_update on the batch k_dqr_sample gathered, or nothing when
@@ -407,9 +449,40 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqr_update(const pm_dqn d, const in
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
     __shared__ float ak[2];
     if (gate[0] < 0) return;  // block-uniform
-    dqn_grads_body(d, sm);
+    dqn_grads_body<false>(d, pm_dqn_opt{}, sm);
     __syncthreads();
-    dqn_apply_body(d, ak);
+    dqn_apply_body<false>(d, pm_dqn_opt{}, ak, nullptr);
+}
+
+// The four with a pm_dqn_opt (pm_dqn_*_opt): the same bodies, the loss chosen in phase 2 and the clip in apply.
+__global__ __launch_bounds__(kDqn, 1) void k_dqn_grads_opt(const pm_dqn d, const pm_dqn_opt o) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    dqn_grads_body<true>(d, o, sm);
+}
+
+__global__ __launch_bounds__(kDqn, 1) void k_dqn_apply_opt(const pm_dqn d, const pm_dqn_opt o) {
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    dqn_apply_body<true>(d, o, ak, nsq);
+}
+
+__global__ __launch_bounds__(kDqn, 1) void k_dqn_update_opt(const pm_dqn d, const pm_dqn_opt o) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    dqn_grads_body<true>(d, o, sm);
+    __syncthreads();
+    dqn_apply_body<true>(d, o, ak, nsq);
+}
+
+__global__ __launch_bounds__(kDqn, 1) void k_dqr_update_opt(const pm_dqn d, const pm_dqn_opt o, const int64_t* gate) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    if (gate[0] < 0) return;  // block-uniform: a void update takes no step and leaves *o.norm as it is
+    dqn_grads_body<true>(d, o, sm);
+    __syncthreads();
+    dqn_apply_body<true>(d, o, ak, nsq);
 }
 
 int check(const pm_dqn* d) {
@@ -421,6 +494,23 @@ int check(const pm_dqn* d) {
                "pm_dqn: noise %d (PM_FOLD_TRAIN or PM_FOLD_TRAIN_FRESH)", d->noise);
     PM_REQUIRE(d->target_update_interval >= 1, PM_E_ARG, "pm_dqn: target_update_interval");
     return PM_OK;
+}
+
+// A null opt is the defaults; huber_beta is only ever read with PM_DQN_LOSS_HUBER.
+int check_opt(const pm_dqn_opt* o) {
+    if (!o) return PM_OK;
+    PM_REQUIRE(o->loss == PM_DQN_LOSS_SQUARED || o->loss == PM_DQN_LOSS_HUBER, PM_E_ARG,
+               "pm_dqn_opt: loss %d (PM_DQN_LOSS_SQUARED or PM_DQN_LOSS_HUBER)", o->loss);
+    PM_REQUIRE(o->loss != PM_DQN_LOSS_HUBER || (std::isfinite(o->huber_beta) && o->huber_beta > 0.0), PM_E_ARG,
+               "pm_dqn_opt: huber_beta %g (> 0, finite)", o->huber_beta);
+    PM_REQUIRE(std::isfinite(o->max_norm) && o->max_norm >= 0.0, PM_E_ARG, "pm_dqn_opt: max_norm %g (0: no clip; > 0, finite)",
+               o->max_norm);
+    return PM_OK;
+}
+
+pm_dqn_opt opt_or_default(const pm_dqn_opt* o) {
+    pm_dqn_opt z{};  // PM_DQN_LOSS_SQUARED, max_norm 0, norm null
+    return o ? *o : z;
 }
 
 int dqn_grads(const pm_dqn* d, void* stream) {
@@ -444,6 +534,14 @@ int dqn_launch_update_gated(const pm_dqn* d, const int64_t* gate, hipStream_t st
     PM_LAUNCHED("k_dqr_update");
     return PM_OK;
 }
+
+int dqn_check_opt(const pm_dqn_opt* o) { return check_opt(o); }
+
+int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int64_t* gate, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqr_update_opt, dim3(1), dim3(kDqn), 0, st, *d, opt_or_default(o), gate);
+    PM_LAUNCHED("k_dqr_update_opt");
+    return PM_OK;
+}
 }  // namespace pm
 
 using namespace pm;
@@ -462,5 +560,31 @@ extern "C" int pm_dqn_update(const pm_dqn* d, void* stream) {
     if (int rc = check(d)) return rc;
     hipLaunchKernelGGL(k_dqn_update, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d);
     PM_LAUNCHED("k_dqn_update");
+    return PM_OK;
+}
+
+extern "C" size_t pm_dqn_opt_sizeof(void) { return sizeof(pm_dqn_opt); }
+
+extern "C" int pm_dqn_grads_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    if (int rc = check(d)) return rc;
+    if (int rc = check_opt(o)) return rc;
+    hipLaunchKernelGGL(k_dqn_grads_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
+    PM_LAUNCHED("k_dqn_grads_opt");
+    return PM_OK;
+}
+
+extern "C" int pm_dqn_apply_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    if (int rc = check(d)) return rc;
+    if (int rc = check_opt(o)) return rc;
+    hipLaunchKernelGGL(k_dqn_apply_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
+    PM_LAUNCHED("k_dqn_apply_opt");
+    return PM_OK;
+}
+
+extern "C" int pm_dqn_update_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    if (int rc = check(d)) return rc;
+    if (int rc = check_opt(o)) return rc;
+    hipLaunchKernelGGL(k_dqn_update_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
+    PM_LAUNCHED("k_dqn_update_opt");
     return PM_OK;
 }

@@ -10,7 +10,8 @@
 //                  then four lanes per sample copy its 64-byte row, one 16-byte load each, into the
 //                  learner's own batch buffers. A tree without mass, or a slot outside [0, size), makes
 //                  the update void: idx <- -1, a status bit, nothing gathered.
-//   k_dqr_update   pm_dqn.hip: k_dqn_update's two bodies, skipped when idx[0] < 0.
+//   k_dqr_update   pm_dqn.hip: k_dqn_update's two bodies, skipped when idx[0] < 0 (pm_dqn_replay_update_opt:
+//                  k_dqr_update_opt, the same with a pm_dqn_opt's loss and clip).
 //   k_dqr_scatter  1024 threads. (1) thread j < batch: the last duplicate of a slot in batch order wins
 //                  (k_per_update's rule) and stores prios[i] = td[j] + 1e-6f and leaf[i] = prio_pow(..);
 //                  every wave drains its stores, barrier. (2) four lanes per sample recompute the level-1
@@ -224,8 +225,12 @@ __global__ __launch_bounds__(256) void k_push_chunks(int64_t cap, int64_t pos, i
 
 extern "C" size_t pm_dqn_replay_sizeof(void) { return sizeof(pm_dqn_replay); }
 
-extern "C" int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates, void* stream) {
+// pm_dqn_replay_update (with_opt false: k_dqr_update in the middle) and pm_dqn_replay_update_opt (k_dqr_update_opt).
+static int replay_update(const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const pm_dqn_replay* rp, int32_t updates,
+                         void* stream) {
     if (int rc = dqn_check(d)) return rc;
+    if (with_opt)
+        if (int rc = dqn_check_opt(o)) return rc;
     PM_REQUIRE(rp, PM_E_ARG, "pm_dqn_replay_update: null replay descriptor");
     PM_REQUIRE(d->isw, PM_E_ARG, "pm_dqn_replay_update: null isw (the draw's weights are written there)");
     PM_REQUIRE(rp->trans && rp->prios && rp->per_work && rp->idx, PM_E_ARG, "pm_dqn_replay_update: null replay buffer");
@@ -239,11 +244,21 @@ extern "C" int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, in
     for (int k = 0; k < updates; ++k) {
         hipLaunchKernelGGL(k_dqr_sample, dim3(1), dim3(256), 0, st, *d, *rp, k);
         PM_LAUNCHED("k_dqr_sample");
-        if (int rc = dqn_launch_update_gated(d, rp->idx, st)) return rc;
+        if (int rc = with_opt ? dqn_launch_update_gated_opt(d, o, rp->idx, st) : dqn_launch_update_gated(d, rp->idx, st))
+            return rc;
         hipLaunchKernelGGL(k_dqr_scatter, dim3(1), dim3(kScatter), 0, st, *d, *rp);
         PM_LAUNCHED("k_dqr_scatter");
     }
     return PM_OK;
+}
+
+extern "C" int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates, void* stream) {
+    return replay_update(d, false, nullptr, rp, updates, stream);
+}
+
+extern "C" int pm_dqn_replay_update_opt(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_replay* rp, int32_t updates,
+                                        void* stream) {
+    return replay_update(d, true, o, rp, updates, stream);
 }
 
 extern "C" int pm_replay_push(float* trans, float* prios, void* per_work, int64_t cap, int64_t pos, float alpha, float prio,

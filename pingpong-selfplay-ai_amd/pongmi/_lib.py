@@ -35,6 +35,7 @@ PM_DQN_NPARAM = 5192
 PM_TRANS_F = 16
 PM_MAX_BATCH = 256
 PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
+PM_DQN_LOSS_SQUARED, PM_DQN_LOSS_HUBER = 0, 1
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
@@ -117,6 +118,10 @@ class DqnReplay(ctypes.Structure):
          ("seed", c_u64)]
 
 
+class DqnOpt(ctypes.Structure):
+    _fields_ = [("loss", c_i32), ("_pad", c_i32), ("huber_beta", c_double), ("max_norm", c_double), ("norm", c_void_p)]
+
+
 class RnnCtrl(ctypes.Structure):
     _fields_ = [("step", c_u64), ("episodes", c_i64), ("seq_count", c_i64), ("seq_size", c_i64), ("epsilon", c_double),
                 ("win_A", c_i64), ("ep_A", c_i64), ("win_P", c_i64), ("ep_P", c_i64), ("reward_B", c_double),
@@ -184,6 +189,11 @@ _SIGS = {
     "pm_dqn_update": (c_i32, [c_void_p, c_void_p]),
     "pm_dqn_replay_sizeof": (ctypes.c_size_t, []),
     "pm_dqn_replay_update": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p]),
+    "pm_dqn_opt_sizeof": (ctypes.c_size_t, []),
+    "pm_dqn_grads_opt": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_apply_opt": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_update_opt": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_replay_update_opt": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_replay_push": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),
@@ -265,6 +275,9 @@ def load():
     if L.pm_dqn_replay_sizeof() != ctypes.sizeof(DqnReplay):  # additive to ABI 27: its own size function
         raise PongmiError(f"struct layout mismatch for DqnReplay: C {L.pm_dqn_replay_sizeof()} "
                           f"vs ctypes {ctypes.sizeof(DqnReplay)}")
+    if L.pm_dqn_opt_sizeof() != ctypes.sizeof(DqnOpt):  # likewise
+        raise PongmiError(f"struct layout mismatch for DqnOpt: C {L.pm_dqn_opt_sizeof()} "
+                          f"vs ctypes {ctypes.sizeof(DqnOpt)}")
     _lib = L
     return L
 

@@ -4,7 +4,8 @@ the caller supplies.
 DQNLearner owns modelB's and targetB's packed QNet blocks (pongmi.qnet layout), the Adam moments and
 the batch buffers; update() runs one train_step on (s, a, r, s', done[, isw]) as one pm_dqn_update
 call — modelB on s and s', targetB (eval mode) on s', the double-DQN target, the importance-weighted
-squared loss, the backward, Adam and the target sync — with no host synchronisation, and returns the
+squared loss (or, with loss="huber", smooth-L1), the backward, Adam (with max_norm, behind a clip on
+the gradient's total norm) and the target sync — with no host synchronisation, and returns the
 device tensor of |q - t| for pongmi.replay.per_update. It is the update a caller with a replay of
 their own runs; the fused self-play step (pongmi.selfplay.SelfPlayLearner) keeps its own.
 update_from() runs the same update on batches drawn from a pongmi.replay.DeviceReplay on the device
@@ -19,6 +20,7 @@ rank computes its gradient into `grad` ([PM_DQN_NPARAM] gradients, then a 1 mark
 rank), the ranks sum `grad`, then apply() divides by that count and takes the identical Adam step.
 """
 import ctypes
+import math
 
 import torch
 
@@ -33,14 +35,30 @@ HEAD_SHAPES = [s for _, s in PARAM_LAYOUT[4:12]]  # list(fc_V.parameters()) + li
 
 class DQNLearner:
     def __init__(self, modelB, target=None, *, batch=256, gamma=0.99, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8,
-                 target_update_interval=1000, train_features=False, fresh_noise=True, seed=0, device="cuda"):
+                 target_update_interval=1000, train_features=False, fresh_noise=True, seed=0, device="cuda",
+                 loss="mse", huber_beta=1.0, max_norm=None):
         """modelB / target: a QNet module, its state_dict, or a packed [PM_QNET_NP] tensor; target None = a
-        copy of modelB (copy.deepcopy(modelB), :100). batch: the most rows an update takes (1..256)."""
+        copy of modelB (copy.deepcopy(modelB), :100). batch: the most rows an update takes (1..256).
+        loss: "mse" (the reference's importance-weighted squared loss) or "huber"
+        ((isw * F.smooth_l1_loss(q, t, reduction='none', beta=huber_beta)).mean()). max_norm: None, or
+        clip_grad_norm_(the trained parameters, max_norm) between the gradient and Adam; stats() then
+        also reports the total norm before the clip. With both at their defaults every call goes to the
+        plain entry points."""
         self.lib = _lib.load()
-        self.device = torch.device(device)
         self.batch = int(batch)
         if not 1 <= self.batch <= PM_MAX_BATCH:
             raise ValueError(f"DQNLearner: batch {self.batch} (1..{PM_MAX_BATCH})")
+        if loss not in ("mse", "huber"):
+            raise ValueError(f"DQNLearner: loss {loss!r} ('mse' or 'huber')")
+        huber_beta = float(huber_beta)
+        if not (math.isfinite(huber_beta) and huber_beta > 0):  # whichever loss: a bad value never waits for a switch
+            raise ValueError(f"DQNLearner: huber_beta {huber_beta} (> 0, finite)")
+        if max_norm is not None:
+            max_norm = float(max_norm)
+            if not (math.isfinite(max_norm) and max_norm > 0):
+                raise ValueError(f"DQNLearner: max_norm {max_norm} (None, or > 0 and finite)")
+        self.loss, self.huber_beta, self.max_norm = loss, huber_beta, max_norm
+        self.device = torch.device(device)
         self.train_features = bool(train_features)
         self.params = self._block(modelB)
         self.target = self._block(target) if target is not None else self.params.clone()
@@ -71,6 +89,15 @@ class DQNLearner:
             float(eps)
         d.seed_net = int(seed)
         self.desc = d
+        # the options: None routes every call to the plain entry points, a pm_dqn_opt to the _opt ones
+        self.opt = None
+        self.norm = None
+        if loss != "mse" or max_norm is not None:
+            if max_norm is not None:
+                self.norm = torch.zeros(1, **f32)  # total norm before the clip of the last apply
+            self.opt = _lib.DqnOpt(loss=_lib.PM_DQN_LOSS_HUBER if loss == "huber" else _lib.PM_DQN_LOSS_SQUARED,
+                                   huber_beta=huber_beta, max_norm=max_norm if max_norm is not None else 0.0,
+                                   norm=self.norm.data_ptr() if self.norm is not None else None)
 
     def _block(self, m):
         if isinstance(m, torch.Tensor):
@@ -96,15 +123,19 @@ class DQNLearner:
         self.desc.isw = self.isw.data_ptr() if isw is not None else None
         self.desc.batch = n
 
-    def _call(self, fn, stream=None):
-        check(fn(ctypes.byref(self.desc), stream_ptr(stream)), fn.__name__)
+    def _call(self, name, stream=None):
+        if self.opt is None:
+            check(getattr(self.lib, name)(ctypes.byref(self.desc), stream_ptr(stream)), name)
+        else:
+            check(getattr(self.lib, name + "_opt")(ctypes.byref(self.desc), ctypes.byref(self.opt), stream_ptr(stream)),
+                  name + "_opt")
 
     def update(self, *batch, isw=None, stream=None):
         """One train_step; batch = (s, a, r, ns, done[, isw]) or nothing (buffers already filled).
         Returns |q - t| per row (a view of the device buffer `td`): update_priorities' errors (:163)."""
         if batch:
             self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
-        self._call(self.lib.pm_dqn_update, stream)
+        self._call("pm_dqn_update", stream)
         return self.td[:self.desc.batch]
 
     def update_from(self, replay, updates=1, *, beta_start=0.4, beta_frames=100000, seed=0, uniforms=None, stream=None):
@@ -128,19 +159,23 @@ class DQNLearner:
                             idx=self.idx.data_ptr(), u=u.data_ptr() if u is not None else None, cap=replay.cap,
                             size=replay.size, alpha=replay.alpha, beta_start=float(beta_start),
                             beta_frames=int(beta_frames), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-        check(self.lib.pm_dqn_replay_update(ctypes.byref(self.desc), ctypes.byref(rp), updates, stream_ptr(stream)),
-              "pm_dqn_replay_update")
+        if self.opt is None:
+            check(self.lib.pm_dqn_replay_update(ctypes.byref(self.desc), ctypes.byref(rp), updates, stream_ptr(stream)),
+                  "pm_dqn_replay_update")
+        else:
+            check(self.lib.pm_dqn_replay_update_opt(ctypes.byref(self.desc), ctypes.byref(self.opt), ctypes.byref(rp),
+                                                    updates, stream_ptr(stream)), "pm_dqn_replay_update_opt")
         replay.max_prio_stale = True
         return self.idx[:n], self.td[:n]
 
     def grads(self, *batch, isw=None, stream=None):
         if batch:
             self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
-        self._call(self.lib.pm_dqn_grads, stream)
+        self._call("pm_dqn_grads", stream)
         return self.td[:self.desc.batch]
 
     def apply(self, stream=None):
-        self._call(self.lib.pm_dqn_apply, stream)
+        self._call("pm_dqn_apply", stream)
 
     # ------------------------------------------------------------------ state
     def _stats(self):
@@ -153,9 +188,13 @@ class DQNLearner:
         self.stats_buf.copy_(torch.frombuffer(bytearray(bytes(s)), dtype=torch.uint8))
 
     def stats(self):
-        """(steps, adam_t, loss, mean q) of the last update (host sync)."""
+        """(steps, adam_t, loss, mean q) of the last update (host sync); on a learner built with max_norm
+        also `norm`, the total gradient norm before the clip of the last apply."""
         s = self._stats()
-        return dict(steps=s.steps, adam_t=s.adam_t, loss=s.loss, q_mean=s.q_mean, status=s.status)
+        out = dict(steps=s.steps, adam_t=s.adam_t, loss=s.loss, q_mean=s.q_mean, status=s.status)
+        if self.norm is not None:
+            out["norm"] = float(self.norm.cpu()[0])
+        return out
 
     def state_dict(self):
         """modelB's state_dict (reference key names; the epsilon buffers hold the last update's noise)."""
