@@ -515,6 +515,48 @@ int pm_dqn_replay_update(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updat
 int pm_dqn_replay_update_opt(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, int32_t updates,
                              void* stream);
 
+/* A population of stand-alone learners (additive to ABI 27 as pm_dqn_opt was: pm_sizeof unchanged; the handle
+ * is opaque, as pm_comm). n independent members, member p being (d[p], opt[p], rp[p]): its own modelB / targetB
+ * blocks, Adam state, counters, hyper-parameters, loss and clip options, batch buffers and, with rp, its own
+ * prioritized replay. Every launch has a grid of n workgroups and workgroup p runs member p from a device table
+ * of the members' descriptors; n may exceed the number of compute units (the workgroups then queue). No
+ * workgroup waits for another and there is no atomic but the one on a member's own status word.
+ *   pm_dqn_pop_create  d, opt and rp are HOST arrays of n entries, free to reuse once it returns. opt may be
+ *     null and a zeroed entry means the defaults; rp may be null: the population then has no replay path.
+ *     Everything is validated on the host before the first HIP call (so a machine without a GPU reports the
+ *     same codes), then the table is allocated and uploaded with a synchronous copy.
+ *   pm_dqn_pop_rebind  replaces the table for the same n (a changed row count `batch`, replay fill `size`,
+ *     uniforms pointer `u`, hyper-parameter, ...) after the same validation. It waits for `stream` before it
+ *     overwrites the table, since launches already queued there read the old one.
+ *   That wait and create's upload are the interface's ONLY host synchronisations: pm_dqn_pop_update and
+ *   pm_dqn_pop_replay_update only enqueue launches.
+ *   pm_dqn_pop_update  one launch. Member p's buffers afterwards hold bit for bit what
+ *     pm_dqn_update_opt(&d[p], &opt[p]) leaves (with default options: what pm_dqn_update(&d[p]) leaves).
+ *   pm_dqn_pop_replay_update  `updates` x three launches (draw + gather, update, scatter + tree refresh).
+ *     Member p's result is bit for bit that of pm_dqn_replay_update_opt(&d[p], &opt[p], &rp[p], updates):
+ *     prios, all three levels of per_work, idx, isw and the batch buffers included; uniform j of update k is
+ *     rp[p].u[k * d[p].batch + j], or Philox where u is null. A member whose update is void keeps its own
+ *     semantics (nothing gathered, no step, idx -1, its status bits latched, its norm untouched) and does not
+ *     disturb the others. PM_E_ARG: a null handle or a population without rp; PM_E_SIZE: updates <= 0.
+ *   pm_dqn_pop_info    n and whether the bound table has replay descriptors (either pointer may be null).
+ *   pm_dqn_pop_destroy frees the table and the handle; the caller has let the launches finish.
+ * Validation (create and rebind), the message naming the offending member index: PM_E_SIZE: n outside
+ * 1..PM_DQN_POP_MAX; PM_E_ARG: a null d or out; per member whatever pm_dqn_update_opt rejects and, with rp,
+ * whatever pm_dqn_replay_update_opt rejects (a null isw included).
+ * Aliasing: a buffer that a launch writes for one member must not overlap, as a byte range of its known size,
+ * any such buffer of another member (PM_E_ARG). Always writable: params, target, adam_m, adam_v, grad, stats,
+ * td, a non-null q, a non-null opt.norm. With rp also: s, ns, act, rew, done, isw, idx, prios, per_work.
+ * Buffers that are only read may be shared: without rp the batch buffers (n members sweeping hyper-parameters
+ * on one batch), with rp the ring trans (one ring of experience, n learners, each with priorities of its own). */
+#define PM_DQN_POP_MAX 1024
+typedef struct pm_dqn_pop pm_dqn_pop;
+int pm_dqn_pop_create(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, int32_t n, pm_dqn_pop** out);
+int pm_dqn_pop_rebind(pm_dqn_pop* pop, const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, void* stream);
+int pm_dqn_pop_update(const pm_dqn_pop* pop, void* stream);
+int pm_dqn_pop_replay_update(const pm_dqn_pop* pop, int32_t updates, void* stream);
+int pm_dqn_pop_info(const pm_dqn_pop* pop, int32_t* n, int32_t* has_replay);
+int pm_dqn_pop_destroy(pm_dqn_pop* pop);
+
 /* memory.push (:56-63) of n caller transitions, 0 < n <= cap, all device buffers: transition i goes to slot
  * (pos + i) mod cap as a PM_TRANS_F row, prios = prio (the caller's max(prios), 1 while empty), leaf =
  * prio^alpha, then the tree nodes overlapping the ring range are recomputed: per_work equals a pm_per_build

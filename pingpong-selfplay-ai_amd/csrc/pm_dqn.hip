@@ -29,9 +29,13 @@
 //     wave sums through LDS under the barrier the body already has, added in wave order by every thread (no
 //     further barrier, no global round trip, no atomic). The bodies are templates; the plain kernels are
 //     their <false> instantiations and keep their device text (tools/kernel_text.py against the parent).
+//   k_dqp_update the population learner's launch (pm_dqn_pop_update, and pm_dqn_pop_replay_update's middle
+//     one): a grid of n workgroups, workgroup p running k_dqr_update_opt's code on the p-th record of a device
+//     table. A member touches its own buffers only, so no workgroup waits for or orders itself against another.
 #include <cmath>
 
 #include "pm_dev.h"
+#include "pm_dqn_pop.h"
 #include "pm_host.h"
 #include "pm_mfma.h"
 
@@ -485,6 +489,18 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqr_update_opt(const pm_dqn d, cons
     dqn_apply_body<true>(d, o, ak, nsq);
 }
 
+// One population member per workgroup: the record is block-uniform and comes in by scalar loads (pm_dqn_pop.h).
+__global__ __launch_bounds__(kDqn, 1) void k_dqp_update(const pm_dqn_member* tab, int gated) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    const pm_dqn_member m = dqp_member(tab);
+    if (gated && m.rp.idx[0] < 0) return;  // block-uniform: this member's update is void; the others' are not
+    dqn_grads_body<true>(m.d, m.o, sm);
+    __syncthreads();
+    dqn_apply_body<true>(m.d, m.o, ak, nsq);
+}
+
 int check(const pm_dqn* d) {
     PM_REQUIRE(d, PM_E_ARG, "pm_dqn: null descriptor");
     PM_REQUIRE(d->params && d->target && d->adam_m && d->adam_v && d->grad && d->stats, PM_E_ARG, "pm_dqn: null buffer");
@@ -540,6 +556,12 @@ int dqn_check_opt(const pm_dqn_opt* o) { return check_opt(o); }
 int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int64_t* gate, hipStream_t st) {
     hipLaunchKernelGGL(k_dqr_update_opt, dim3(1), dim3(kDqn), 0, st, *d, opt_or_default(o), gate);
     PM_LAUNCHED("k_dqr_update_opt");
+    return PM_OK;
+}
+
+int dqp_launch_update(const pm_dqn_member* tab, int n, int gated, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqp_update, dim3(n), dim3(kDqn), 0, st, tab, gated);
+    PM_LAUNCHED("k_dqp_update");
     return PM_OK;
 }
 }  // namespace pm

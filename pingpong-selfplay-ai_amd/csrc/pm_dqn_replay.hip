@@ -23,7 +23,10 @@
 //                  per_quarter takes them const __restrict__, which may not be mixed with stores to them).
 //   A recomputed node is the same additions in the same order as a rebuild's, so the workspace equals
 //   pm_per_build(prios) bit for bit after every update, and the next one draws from it as it is.
+//   k_dqp_sample / k_dqp_scatter are the population learner's (pm_dqn_pop_replay_update, pm_dqn_pop.hip): a grid
+//   of n workgroups, workgroup p running the same body on the p-th record of a device table (pm_dqn_pop.h).
 #include "pm_dev.h"
+#include "pm_dqn_pop.h"
 #include "pm_host.h"
 #include "pm_per.h"
 
@@ -45,66 +48,16 @@ struct DqrSampleSmem {
 
 __global__ __launch_bounds__(256) void k_dqr_sample(const pm_dqn d, const pm_dqn_replay rp, int upd) {
     __shared__ DqrSampleSmem sm;
-    const int t = threadIdx.x, wv = t >> 6, B = d.batch;
-    const int64_t frame = d.stats->steps + 1;  // frame_idx += 1 before sampling (:136)
-    const double b = rp.beta_start + (double)frame * (1.0 - rp.beta_start) / (double)rp.beta_frames;  // :137
-    const double beta = b < 1.0 ? b : 1.0;
-    const PerTree tr = per_tree(rp.per_work, rp.cap);
-    const double* u = rp.u ? rp.u + (size_t)upd * B : nullptr;
-    int bad = 0;
-    for (int j0 = 0; j0 < B; j0 += PER_BS)
-        per_sample_block<true>(
-            true, rp.size, tr, PushRange{0, 0, rp.cap, 0.f}, beta, j0, B, sm.per,
-            [&](int j) {
-                if (u) return u[j];
-                const U4 r = philox64((uint32_t)j, TAG_PER, (uint64_t)frame, rp.seed);
-                return u53(r.x, r.y);
-            },
-            [&](int j, int64_t i, double pa, double total) {
-                sm.sidx[j] = i;
-                sm.w[j] = per_is_weight(rp.size, pa, total, beta);
-                if (!(total > 0.0)) bad |= DQR_NO_MASS;
-                else if (i < 0 || i >= rp.size) bad |= DQR_BAD_SLOT;
-            });
-    const int no_mass = __syncthreads_or(bad & DQR_NO_MASS), bad_slot = __syncthreads_or(bad & DQR_BAD_SLOT);
-    if (no_mass || bad_slot) {  // block-uniform: a void update
-        if (t < B) rp.idx[t] = -1;
-        if (t == 0) atomicOr(&d.stats->status, (no_mass ? DQR_NO_MASS : 0) | (bad_slot ? DQR_BAD_SLOT : 0));
-        return;
-    }
-    {
-        const float m = wave_max(t < B ? sm.w[t] : 0.f);
-        if ((t & 63) == 0) sm.red[wv] = m;
-    }
-    __syncthreads();
-    const float mx = fmaxf(fmaxf(sm.red[0], sm.red[1]), fmaxf(sm.red[2], sm.red[3]));
-    // the batch buffers are the learner's own: pm_dqn declares them const for the entry points that only read them
-    float* const s = const_cast<float*>(d.s);
-    float* const ns = const_cast<float*>(d.ns);
-    float* const rew = const_cast<float*>(d.rew);
-    float* const isw = const_cast<float*>(d.isw);
-    int32_t* const act = const_cast<int32_t*>(d.act);
-    uint8_t* const done = const_cast<uint8_t*>(d.done);
-    const int q = t & 3;
-    for (int j = t >> 2; j < B; j += PER_BS) {
-        const int64_t i = sm.sidx[j];  // in [0, size): checked above
-        const float4 x = reinterpret_cast<const float4*>(rp.trans + i * PM_TRANS_F)[q];
-        float* const o = (q < 2 ? s : ns) + (size_t)j * 7 + 4 * (q & 1);
-        o[0] = x.x; o[1] = x.y; o[2] = x.z;
-        if (q == 0) {
-            o[3] = x.w;
-            rp.idx[j] = i;
-            isw[j] = sm.w[j] / mx;  // k_per_normalize's division
-        } else if (q == 1) {
-            rew[j] = x.w;
-        } else if (q == 2) {
-            o[3] = x.w;
-        } else {
-            const int bits = __float_as_int(x.w);
-            act[j] = bits & 0xff;
-            done[j] = (uint8_t)((bits >> 8) & 1);
-        }
-    }
+#include "pm_dqr_sample_body.inc"
+}
+
+// The population's draw + gather: workgroup p draws from member p's own tree into member p's own batch buffers.
+__global__ __launch_bounds__(256) void k_dqp_sample(const pm_dqn_member* tab, int upd) {
+    __shared__ DqrSampleSmem sm;
+    const pm_dqn_member m = dqp_member(tab);
+    const pm_dqn& d = m.d;
+    const pm_dqn_replay& rp = m.rp;
+#include "pm_dqr_sample_body.inc"
 }
 
 typedef float f32x4n __attribute__((ext_vector_type(4)));
@@ -140,8 +93,8 @@ __device__ __forceinline__ double dqr_chunk_sum(const PerTree& t, int64_t c) {
     return acc;
 }
 
-__global__ __launch_bounds__(kScatter) void k_dqr_scatter(const pm_dqn d, const pm_dqn_replay rp) {
-    __shared__ int64_t sidx[PM_MAX_BATCH];
+// k_dqr_scatter's body, block-wide (kScatter threads); sidx: PM_MAX_BATCH slots of LDS.
+__device__ __forceinline__ void dqr_scatter_body(const pm_dqn& d, const pm_dqn_replay& rp, int64_t* sidx) {
     const int t = threadIdx.x, B = d.batch;
     if (rp.idx[0] < 0) return;  // a void update (block-uniform)
     const PerTree tr = per_tree(rp.per_work, rp.cap);
@@ -176,6 +129,18 @@ __global__ __launch_bounds__(kScatter) void k_dqr_scatter(const pm_dqn d, const 
         const int64_t c = i / PER_CHUNK;
         tr.chunk[c] = dqr_chunk_sum(tr, c);
     }
+}
+
+__global__ __launch_bounds__(kScatter) void k_dqr_scatter(const pm_dqn d, const pm_dqn_replay rp) {
+    __shared__ int64_t sidx[PM_MAX_BATCH];
+    dqr_scatter_body(d, rp, sidx);
+}
+
+// The population's scatter + tree refresh: member p's priorities and member p's tree only.
+__global__ __launch_bounds__(kScatter) void k_dqp_scatter(const pm_dqn_member* tab) {
+    __shared__ int64_t sidx[PM_MAX_BATCH];
+    const pm_dqn_member m = dqp_member(tab);
+    dqr_scatter_body(m.d, m.rp, sidx);
 }
 
 // ----------------------------------------------------------------------------- pm_replay_push
@@ -225,12 +190,8 @@ __global__ __launch_bounds__(256) void k_push_chunks(int64_t cap, int64_t pos, i
 
 extern "C" size_t pm_dqn_replay_sizeof(void) { return sizeof(pm_dqn_replay); }
 
-// pm_dqn_replay_update (with_opt false: k_dqr_update in the middle) and pm_dqn_replay_update_opt (k_dqr_update_opt).
-static int replay_update(const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const pm_dqn_replay* rp, int32_t updates,
-                         void* stream) {
-    if (int rc = dqn_check(d)) return rc;
-    if (with_opt)
-        if (int rc = dqn_check_opt(o)) return rc;
+// The replay side of pm_dqn_replay_update's checks (pm_dqn_pop_create runs them per member, updates = 1).
+int pm::dqn_replay_check(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates) {
     PM_REQUIRE(rp, PM_E_ARG, "pm_dqn_replay_update: null replay descriptor");
     PM_REQUIRE(d->isw, PM_E_ARG, "pm_dqn_replay_update: null isw (the draw's weights are written there)");
     PM_REQUIRE(rp->trans && rp->prios && rp->per_work && rp->idx, PM_E_ARG, "pm_dqn_replay_update: null replay buffer");
@@ -240,6 +201,28 @@ static int replay_update(const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, co
                (long long)rp->size, (long long)rp->cap);
     PM_REQUIRE(updates > 0, PM_E_SIZE, "pm_dqn_replay_update: updates=%d", updates);
     PM_REQUIRE(rp->beta_frames > 0, PM_E_SIZE, "pm_dqn_replay_update: beta_frames=%lld", (long long)rp->beta_frames);
+    return PM_OK;
+}
+
+int pm::dqp_launch_sample(const pm_dqn_member* tab, int n, int upd, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqp_sample, dim3(n), dim3(256), 0, st, tab, upd);
+    PM_LAUNCHED("k_dqp_sample");
+    return PM_OK;
+}
+
+int pm::dqp_launch_scatter(const pm_dqn_member* tab, int n, hipStream_t st) {
+    hipLaunchKernelGGL(k_dqp_scatter, dim3(n), dim3(kScatter), 0, st, tab);
+    PM_LAUNCHED("k_dqp_scatter");
+    return PM_OK;
+}
+
+// pm_dqn_replay_update (with_opt false: k_dqr_update in the middle) and pm_dqn_replay_update_opt (k_dqr_update_opt).
+static int replay_update(const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const pm_dqn_replay* rp, int32_t updates,
+                         void* stream) {
+    if (int rc = dqn_check(d)) return rc;
+    if (with_opt)
+        if (int rc = dqn_check_opt(o)) return rc;
+    if (int rc = dqn_replay_check(d, rp, updates)) return rc;
     hipStream_t st = pm_stream(stream);
     for (int k = 0; k < updates; ++k) {
         hipLaunchKernelGGL(k_dqr_sample, dim3(1), dim3(256), 0, st, *d, *rp, k);

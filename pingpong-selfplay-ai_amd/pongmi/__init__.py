@@ -7,6 +7,7 @@
   pongmi.selfplay  SelfPlayLearner: the batched train_iterative loop (K1+K2+K4+K3)
   pongmi.dqn       DQNLearner: train_step on a caller's batch, heads only or the whole QNet (K10), or drawn
                    from a DeviceReplay (update_from, K11); ReplayTrainer: collect and train
+  pongmi.dqn_pop   DQNPopulation: n such learners trained with one launch per phase (K12)
 """
 from ._lib import PongmiError, load  # noqa: F401
 

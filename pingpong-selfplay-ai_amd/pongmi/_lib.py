@@ -36,6 +36,7 @@ PM_TRANS_F = 16
 PM_MAX_BATCH = 256
 PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
 PM_DQN_LOSS_SQUARED, PM_DQN_LOSS_HUBER = 0, 1
+PM_DQN_POP_MAX = 1024
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
@@ -194,6 +195,12 @@ _SIGS = {
     "pm_dqn_apply_opt": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "pm_dqn_update_opt": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "pm_dqn_replay_update_opt": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
+    "pm_dqn_pop_create": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, ctypes.POINTER(c_void_p)]),
+    "pm_dqn_pop_rebind": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_pop_update": (c_i32, [c_void_p, c_void_p]),
+    "pm_dqn_pop_replay_update": (c_i32, [c_void_p, c_i32, c_void_p]),
+    "pm_dqn_pop_info": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_pop_destroy": (c_i32, [c_void_p]),
     "pm_replay_push": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),

@@ -10,7 +10,8 @@ device tensor of |q - t| for pongmi.replay.per_update. It is the update a caller
 their own runs; the fused self-play step (pongmi.selfplay.SelfPlayLearner) keeps its own.
 update_from() runs the same update on batches drawn from a pongmi.replay.DeviceReplay on the device
 (pm_dqn_replay_update: draw, gather, update, priority scatter, incremental tree refresh), and
-ReplayTrainer alternates it with the collecting rollout.
+ReplayTrainer alternates it with the collecting rollout. DQNPopulation (pongmi.dqn_pop) trains n such
+learners with one launch per phase.
 
 train_features=False trains the 520 NoisyNet head parameters, as the reference does (it freezes
 modelB.features, :97); train_features=True trains all 5 192 parameters of the QNet.
@@ -272,3 +273,6 @@ class ReplayTrainer:
                                      beta_frames=self.beta_frames, seed=self.seed)
             self.rollout.set_paramsB(self.learner.params)
         return dict(zip(STATS_PUSH, (int(v) for v in total.cpu().tolist())))
+
+
+from .dqn_pop import DQNPopulation  # noqa: E402,F401  (pongmi.dqn.DQNPopulation; dqn_pop imports DQNLearner from here)
