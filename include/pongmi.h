@@ -278,6 +278,63 @@ int pm_rollout_push(const pm_env_params* p, const pm_env_state* s, const float* 
                     int32_t steps, float* heads_ws, float* obsA, float* obsB, const pm_roll_replay* rp, int64_t* stats,
                     int32_t n, void* stream);
 
+/* The collecting rollout for a population (csrc/pm_rollout_pop.hip; additive to ABI 27 as pm_dqn_pop was:
+ * pm_sizeof unchanged, a size function of its own, an opaque handle). n members of m arenas each play in one
+ * launch per phase: member p owns arenas [p * m, (p + 1) * m) of ONE pm_env_state of n * m arenas (one
+ * pm_env_params for all), plays its own opponent wA against its own modelB (wB / paramsB) and pushes into its
+ * own prioritized replay. Member p's arenas, observations, ep_reward, ring rows, prios, PER leaves, tree nodes
+ * and stats afterwards hold bit for bit what pm_rollout_push leaves for an m-arena state equal to the member's
+ * slice with the member's wA, wB, paramsB, epsilon, seed_env, seed_net, the call's counter0 and the member's
+ * current pos and pushed priority: every Philox draw is keyed by the member-local arena index 0..m-1.
+ *   pm_roll_member  member p's record (a HOST array of n, free to reuse once create / rebind returns).
+ *     rp.ep_reward is the member's own [m]; rp.pos / size are the ring's write slot and fill WHEN THE TABLE WAS
+ *     BOUND; rp.prio is the pushed priority unless prio_dev is set (below). stats (nullable): the member's own
+ *     6 x int64, accumulated (pm_rollout_push's six entries).
+ *   pm_rollout_pop_create / _rebind  validate everything on the host before the first HIP call (so a machine
+ *     without a GPU reports the same codes, the message naming the member), then upload the table with a
+ *     synchronous copy; rebind (same n, m, steps_max) first waits for `stream`, since launches queued there
+ *     read the old table. These are the interface's ONLY host synchronisations.
+ *   pm_rollout_pop_push  only enqueues launches: `steps` vector steps (0 <= steps <= steps_max; 0 is a no-op)
+ *     from Philox counter counter0. `advance` (>= 0) is the number of transitions each member has pushed since
+ *     the table was bound (every member pushes steps * m per call, so it is one number): the launch writes from
+ *     pos = (rp.pos + advance) mod cap into a ring of fill min(cap, size + advance), so a loop of collects never
+ *     rebinds. In stream order: for members with prio_dev, prio_dev[0] = max(prios[0:fill]) (1.0f when the fill
+ *     is 0: PrioritizedReplay.push's max(prios), taken on the device with no host read) and that value is the
+ *     priority pushed; the heads of every (step, member); the rollout (one block per member and 32-arena tile);
+ *     the tree nodes of every member with per_work. obsA / obsB are [n * m][7].
+ *   pm_rollout_pop_info  n, m and steps_max (any pointer may be null). _destroy frees table and handle; the
+ *     caller has let the launches finish.
+ * PM_E_SIZE: n outside 1..PM_DQN_POP_MAX, m < 1, n * m past int32, steps_max < 1, steps outside 0..steps_max,
+ * advance < 0; per member cap <= 0, pos outside [0, cap), size outside [0, cap], steps_max * m > cap (a slot
+ * would be written twice in one launch). PM_E_ARG: a null handle, out, members, p, s or state / observation
+ * array; speed_scale_every <= 0; per member a null wA, wB, paramsB, heads_ws, trans, prios or ep_reward; wA, wB,
+ * heads_ws, trans or per_work not 16-byte aligned; epsilon not finite.
+ * Aliasing (PM_E_ARG): trans, prios, per_work, ep_reward, heads_ws, stats, prio_dev and wB of one member must not
+ * overlap, as byte ranges of their known sizes, any of those of another member. wA and paramsB are only read
+ * and may be shared. */
+typedef struct pm_roll_member {
+    const float *wA;       /* the opponent's effective weights, PM_QNET_NW, 16-byte aligned */
+    float *wB;             /* the member's feature image: any fold of paramsB, PM_QNET_NW, 16-byte aligned */
+    const float *paramsB;  /* PM_QNET_NP, read in place */
+    float *heads_ws;       /* steps_max * PM_ROLL_HEADS floats, 16-byte aligned */
+    pm_roll_replay rp;
+    int64_t size;          /* the ring's fill when the table was bound, 0..cap */
+    float *prio_dev;       /* nullable, device [1]: see pm_rollout_pop_push */
+    int64_t *stats;        /* nullable, device [6], accumulated */
+    float epsilon;
+    int32_t _pad;
+    uint64_t seed_env, seed_net;
+} pm_roll_member;
+size_t pm_roll_member_sizeof(void);
+typedef struct pm_rollout_pop pm_rollout_pop;
+int pm_rollout_pop_create(const pm_env_params* p, const pm_env_state* s, const pm_roll_member* members, int32_t n,
+                          int32_t m, int32_t steps_max, pm_rollout_pop** out);
+int pm_rollout_pop_rebind(pm_rollout_pop* pop, const pm_roll_member* members, void* stream);
+int pm_rollout_pop_push(const pm_rollout_pop* pop, uint64_t counter0, int32_t steps, int64_t advance, float* obsA,
+                        float* obsB, void* stream);
+int pm_rollout_pop_info(const pm_rollout_pop* pop, int32_t* n, int32_t* m, int32_t* steps_max);
+int pm_rollout_pop_destroy(pm_rollout_pop* pop);
+
 /* ---------------------------------------------------------------- QNetRNN (K5) */
 
 /* Packed QNetRNN parameter block (models/qnet_rnn.py:58-101), PM_RNN_NP floats: the state_dict

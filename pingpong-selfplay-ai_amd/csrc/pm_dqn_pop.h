@@ -2,6 +2,8 @@
 // units share: pm_dqn_pop.hip owns the handle, the validation and the device table; the kernels live beside
 // the bodies they call, k_dqp_update in pm_dqn.hip and k_dqp_sample / k_dqp_scatter in pm_dqn_replay.hip.
 #pragma once
+#include <vector>
+
 #include "pm_host.h"
 
 // One row of the device table: workgroup p of every population launch runs tab[p]. rp is all zeros in a
@@ -32,6 +34,19 @@ __device__ __forceinline__ pm_dqn_member dqp_member(const pm_dqn_member* tab) {
     return m;
 }
 #endif
+
+// The populations' aliasing rule (pm_dqn_pop.hip; shared with pm_rollout_pop.hip): a byte range [lo, hi) that a
+// launch may write for `member`, named `kind` in the error.
+struct PopRange {
+    uintptr_t lo, hi;
+    int member;
+    const char* kind;
+};
+void pop_add(std::vector<PopRange>& v, int p, const char* kind, const void* ptr, size_t bytes);  // skips null / empty
+// PM_E_ARG naming both members and buffers if a range of one member meets a range of another. Sorts v.
+int pop_check_overlap(const char* who, std::vector<PopRange>& v);
+// The last error behind "who: member p: ", with code rc.
+int pop_member_fail(int rc, const char* who, int p);
 
 // pm_dqn_replay.hip: what pm_dqn_replay_update checks behind pm_dqn's and pm_dqn_opt's own checks.
 int dqn_replay_check(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates);

@@ -25,27 +25,55 @@ struct pm_dqn_pop {
     int32_t has_replay;
 };
 
-namespace {
+namespace pm {
 
 // A failed per-member check: its message behind the member's index.
-int member_fail(int rc, const char* who, int p) {
+int pop_member_fail(int rc, const char* who, int p) {
     char msg[400];
     snprintf(msg, sizeof(msg), "%s", pm_last_error());
     return pm_fail(rc, "%s: member %d: %s", who, p, msg);
 }
 
-struct Range {
-    uintptr_t lo, hi;  // [lo, hi)
-    int member;
-    const char* kind;
-};
-
-void add(std::vector<Range>& v, int p, const char* kind, const void* ptr, size_t bytes) {
-    if (ptr && bytes) v.push_back(Range{(uintptr_t)ptr, (uintptr_t)ptr + bytes, p, kind});
+void pop_add(std::vector<PopRange>& v, int p, const char* kind, const void* ptr, size_t bytes) {
+    if (ptr && bytes) v.push_back(PopRange{(uintptr_t)ptr, (uintptr_t)ptr + bytes, p, kind});
 }
 
+// No writable byte range of one member may meet one of another's. Sorted by start, a range conflicts exactly
+// when it starts below the furthest end seen so far among the OTHER members' ranges: the furthest end overall
+// (top) and the furthest among members other than top's (other) are enough to know that.
+int pop_check_overlap(const char* who, std::vector<PopRange>& v) {
+    std::sort(v.begin(), v.end(), [](const PopRange& a, const PopRange& b) { return a.lo < b.lo; });
+    const PopRange* top = nullptr;
+    const PopRange* other = nullptr;
+    for (const PopRange& r : v) {
+        const PopRange* hit = nullptr;
+        if (top && top->member != r.member && r.lo < top->hi) hit = top;
+        else if (top && top->member == r.member && other && r.lo < other->hi) hit = other;
+        if (hit) {
+            const PopRange& a = hit->member < r.member ? *hit : r;
+            const PopRange& b = hit->member < r.member ? r : *hit;
+            return pm_fail(PM_E_ARG, "%s: member %d: its %s overlaps member %d's %s (writable buffers must be disjoint)", who,
+                           b.member, b.kind, a.member, a.kind);
+        }
+        if (!top || r.hi > top->hi) {
+            if (top && top->member != r.member && (!other || top->hi > other->hi)) other = top;
+            top = &r;
+        } else if (r.member != top->member && (!other || r.hi > other->hi)) {
+            other = &r;
+        }
+    }
+    return PM_OK;
+}
+
+}  // namespace pm
+
+namespace {
+
+using pm::PopRange;
+constexpr auto add = pm::pop_add;
+
 // Every buffer a launch may write for member p, with its size in bytes.
-void writable(std::vector<Range>& v, int p, const pm_dqn& d, const pm_dqn_opt& o, const pm_dqn_replay* rp) {
+void writable(std::vector<PopRange>& v, int p, const pm_dqn& d, const pm_dqn_opt& o, const pm_dqn_replay* rp) {
     const size_t B = (size_t)d.batch;
     add(v, p, "params", d.params, sizeof(float) * PM_QNET_NP);
     add(v, p, "target", d.target, sizeof(float) * PM_QNET_NP);
@@ -68,33 +96,6 @@ void writable(std::vector<Range>& v, int p, const pm_dqn& d, const pm_dqn_opt& o
     add(v, p, "per_work", rp->per_work, (size_t)pm_per_work_bytes(rp->cap));
 }
 
-// No writable byte range of one member may meet one of another's. Sorted by start, a range conflicts exactly
-// when it starts below the furthest end seen so far among the OTHER members' ranges: the furthest end overall
-// (top) and the furthest among members other than top's (other) are enough to know that.
-int check_overlap(const char* who, std::vector<Range>& v) {
-    std::sort(v.begin(), v.end(), [](const Range& a, const Range& b) { return a.lo < b.lo; });
-    const Range* top = nullptr;
-    const Range* other = nullptr;
-    for (const Range& r : v) {
-        const Range* hit = nullptr;
-        if (top && top->member != r.member && r.lo < top->hi) hit = top;
-        else if (top && top->member == r.member && other && r.lo < other->hi) hit = other;
-        if (hit) {
-            const Range& a = hit->member < r.member ? *hit : r;
-            const Range& b = hit->member < r.member ? r : *hit;
-            return pm_fail(PM_E_ARG, "%s: member %d: its %s overlaps member %d's %s (writable buffers must be disjoint)", who,
-                           b.member, b.kind, a.member, a.kind);
-        }
-        if (!top || r.hi > top->hi) {
-            if (top && top->member != r.member && (!other || top->hi > other->hi)) other = top;
-            top = &r;
-        } else if (r.member != top->member && (!other || r.hi > other->hi)) {
-            other = &r;
-        }
-    }
-    return PM_OK;
-}
-
 // Everything pm_dqn_pop_create and _rebind reject, and the table they upload. No HIP call.
 int build_table(const char* who, const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, int32_t n,
                 std::vector<pm_dqn_member>& tab) {
@@ -102,21 +103,21 @@ int build_table(const char* who, const pm_dqn* d, const pm_dqn_opt* opt, const p
     PM_REQUIRE(d, PM_E_ARG, "%s: null descriptor array", who);
     tab.assign((size_t)n, pm_dqn_member{});
     for (int p = 0; p < n; ++p) {
-        if (int rc = pm::dqn_check(&d[p])) return member_fail(rc, who, p);
+        if (int rc = pm::dqn_check(&d[p])) return pm::pop_member_fail(rc, who, p);
         if (opt)
-            if (int rc = pm::dqn_check_opt(&opt[p])) return member_fail(rc, who, p);
+            if (int rc = pm::dqn_check_opt(&opt[p])) return pm::pop_member_fail(rc, who, p);
         if (rp) {
-            if (int rc = pm::dqn_replay_check(&d[p], &rp[p], 1)) return member_fail(rc, who, p);
+            if (int rc = pm::dqn_replay_check(&d[p], &rp[p], 1)) return pm::pop_member_fail(rc, who, p);
             PM_REQUIRE(rp[p].cap > 0, PM_E_SIZE, "%s: member %d: cap=%lld", who, p, (long long)rp[p].cap);
         }
         tab[p].d = d[p];
         if (opt) tab[p].o = opt[p];
         if (rp) tab[p].rp = rp[p];
     }
-    std::vector<Range> v;
+    std::vector<PopRange> v;
     v.reserve((size_t)n * 18);
     for (int p = 0; p < n; ++p) writable(v, p, tab[p].d, tab[p].o, rp ? &tab[p].rp : nullptr);
-    return check_overlap(who, v);
+    return pm::pop_check_overlap(who, v);
 }
 
 }  // namespace

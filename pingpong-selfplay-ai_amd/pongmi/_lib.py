@@ -86,6 +86,12 @@ class RollReplay(ctypes.Structure):
         [("pos", c_i64), ("cap", c_i64), ("prio", c_float), ("alpha", c_float)]
 
 
+class RollMember(ctypes.Structure):
+    _fields_ = [(n, c_void_p) for n in ("wA", "wB", "paramsB", "heads_ws")] + \
+        [("rp", RollReplay), ("size", c_i64), ("prio_dev", c_void_p), ("stats", c_void_p), ("epsilon", c_float),
+         ("_pad", c_i32), ("seed_env", c_u64), ("seed_net", c_u64)]
+
+
 class DrqnStats(ctypes.Structure):
     _fields_ = [("steps", c_i64), ("adam_t", c_i64), ("loss", c_float), ("norm", c_float), ("q_mean", c_float),
                 ("status", c_i32)]
@@ -201,6 +207,12 @@ _SIGS = {
     "pm_dqn_pop_replay_update": (c_i32, [c_void_p, c_i32, c_void_p]),
     "pm_dqn_pop_info": (c_i32, [c_void_p, c_void_p, c_void_p]),
     "pm_dqn_pop_destroy": (c_i32, [c_void_p]),
+    "pm_roll_member_sizeof": (ctypes.c_size_t, []),
+    "pm_rollout_pop_create": (c_i32, [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, ctypes.POINTER(c_void_p)]),
+    "pm_rollout_pop_rebind": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_rollout_pop_push": (c_i32, [c_void_p, c_u64, c_i32, c_i64, c_void_p, c_void_p, c_void_p]),
+    "pm_rollout_pop_info": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_rollout_pop_destroy": (c_i32, [c_void_p]),
     "pm_replay_push": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),
@@ -285,6 +297,9 @@ def load():
     if L.pm_dqn_opt_sizeof() != ctypes.sizeof(DqnOpt):  # likewise
         raise PongmiError(f"struct layout mismatch for DqnOpt: C {L.pm_dqn_opt_sizeof()} "
                           f"vs ctypes {ctypes.sizeof(DqnOpt)}")
+    if L.pm_roll_member_sizeof() != ctypes.sizeof(RollMember):  # likewise
+        raise PongmiError(f"struct layout mismatch for RollMember: C {L.pm_roll_member_sizeof()} "
+                          f"vs ctypes {ctypes.sizeof(RollMember)}")
     _lib = L
     return L
 

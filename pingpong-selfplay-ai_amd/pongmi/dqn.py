@@ -275,4 +275,43 @@ class ReplayTrainer:
         return dict(zip(STATS_PUSH, (int(v) for v in total.cpu().tolist())))
 
 
+class PopulationTrainer:
+    """ReplayTrainer for a population: run(iterations) alternates
+
+        rollout.collect(collect_steps, sync=False)       # pm_rollout_pop_push: m * collect_steps transitions per member
+        population.update_from(replays, updates)         # pm_dqn_pop_replay_update
+
+    with `rollout` a pongmi.rollout.PopulationRollout over population.params in place (every collect refolds the
+    members' feature images first, so it plays what the learners hold), and returns the accumulated rollout
+    stats (pongmi.rollout.STATS_PUSH) as int64 arrays of n. Member p's rings, learner state and stats are bit for
+    bit those of a ReplayTrainer on a PongEnv2PBatch(m, seed=seed_env[p]) holding the member's slice.
+
+    Host synchronisation: the stats are summed on the device and read once at the end, and the pushed priority
+    max(prios) is taken on the device. While the rings are still filling, DQNPopulation rebinds its table once
+    per iteration (the table holds each ring's fill `size`), which waits for the stream; once every ring is full
+    a run() performs no host synchronisation until that final read."""
+
+    def __init__(self, env, wA, population, replays, *, collect_steps, updates, epsilon=0.02, seed_env=None, seed_net=0,
+                 beta_start=0.4, beta_frames=100000, seed=0):
+        from .rollout import PopulationRollout
+        self.population, self.replays = population, list(replays)
+        self.collect_steps, self.updates = int(collect_steps), int(updates)
+        if self.collect_steps < 1 or self.updates < 1:
+            raise ValueError("PopulationTrainer: collect_steps and updates must be >= 1")
+        self.beta_start, self.beta_frames, self.seed = float(beta_start), int(beta_frames), seed
+        self.rollout = PopulationRollout(env, wA, population.params, n=population.n, replays=self.replays,
+                                         epsilon=epsilon, seed_env=seed_env, seed_net=seed_net,
+                                         steps_max=self.collect_steps)
+
+    def run(self, iterations):
+        from .rollout import STATS_PUSH
+        total = torch.zeros_like(self.rollout.stats)
+        for _ in range(int(iterations)):
+            total += self.rollout.collect(self.collect_steps, sync=False)
+            self.population.update_from(self.replays, self.updates, beta_start=self.beta_start,
+                                        beta_frames=self.beta_frames, seed=self.seed)
+        host = total.cpu().numpy()
+        return {name: host[:, k].copy() for k, name in enumerate(STATS_PUSH)}
+
+
 from .dqn_pop import DQNPopulation  # noqa: E402,F401  (pongmi.dqn.DQNPopulation; dqn_pop imports DQNLearner from here)

@@ -110,3 +110,179 @@ def _weights(t, size, name, device):
     if t.data_ptr() % 16:
         t = t.clone()
     return t
+
+
+def _per_member(name, v, n):
+    """`v` as a list of n values: one value for all members, or a sequence of n (dqn_pop._per_member)."""
+    import numpy as np
+    if not isinstance(v, (list, tuple, np.ndarray, torch.Tensor)):
+        return [v] * n
+    if len(v) != n:
+        raise ValueError(f"PopulationRollout: {name} has {len(v)} values for {n} members")
+    return [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in v]
+
+
+class PopulationRollout:
+    """The collecting rollout for a population (pm_rollout_pop_*, csrc/pm_rollout_pop.hip): n members of m arenas
+    each, member p playing arenas [p * m, (p + 1) * m) of `env` against its own opponent and pushing into its
+    own DeviceReplay, in one launch per phase instead of n solo rollouts. Member p's arenas, observations, ring,
+    priorities, sum tree and stats are bit for bit what SelfPlayRollout.run(steps, replay=replays[p]) leaves on a
+    PongEnv2PBatch(m, seed=seed_env[p]) holding the member's slice (tests/test_gpu_rollout_pop.py).
+
+    env       a PongEnv2PBatch of n * m arenas, autoreset, no serve table. Its counter is every member's Philox
+              step counter; its seed is only the default of seed_env.
+    wA        the opponents' effective weights: one [PM_QNET_NW] net for all members, [n, PM_QNET_NW], or a list
+              of n [PM_QNET_NW] tensors (members given the same tensor read the one copy).
+    params    the members' stacked [n, PM_QNET_NP] modelB blocks, USED IN PLACE (contiguous float32 on the env's
+              device): pass DQNPopulation.params and every collect plays what the learners hold, with no copy.
+    replays   n distinct DeviceReplays, cap >= steps_max * m each; one whose `work` is None keeps no sum tree.
+    epsilon, seed_env, seed_net   one value or n values; seed_env None = env.seed + p.
+    steps_max the most vector steps one collect takes (default: min(32, min(cap) // m)).
+    Bad values raise ValueError before anything is allocated.
+
+    collect(steps) refolds every member's feature image from params in one launch (so a stale image after
+    DQNPopulation.update_from or exploit() cannot be played), runs the launches, advances every replay's pos /
+    size and env.counter, and marks every replay max_prio_stale: the pushed priority max(prios) is taken on the
+    device (no host read), so the replays' tracked max_prio is not kept. The library's table holds each ring's
+    pos / size as of the last bind plus the transitions pushed since; it is rebound, the interface's only host
+    synchronisation after the first collect, only when a replay's pos / size is not what this collector left
+    (someone else pushed into it) or one of its buffers was replaced."""
+
+    def __init__(self, env, wA, params, *, n, replays, epsilon=0.02, seed_env=None, seed_net=0, steps_max=None):
+        import math
+        n = int(n)
+        if not 1 <= n <= _lib.PM_DQN_POP_MAX:
+            raise ValueError(f"PopulationRollout: n {n} (1..{_lib.PM_DQN_POP_MAX})")
+        if env.n < n or env.n % n:
+            raise ValueError(f"PopulationRollout: the env's {env.n} arenas are not n = {n} equal slices")
+        m = env.n // n
+        if env.inject is not None:
+            raise ValueError("PopulationRollout uses production (Philox) serves: the env has a serve table")
+        if env.autoreset != 1:
+            raise ValueError("PopulationRollout needs an autoreset=True env (the rollout never stops an arena)")
+        replays = list(replays)
+        if len(replays) != n:
+            raise ValueError(f"PopulationRollout: {len(replays)} replays for {n} members")
+        if len({id(r) for r in replays}) != n:
+            raise ValueError("PopulationRollout: members cannot share a replay while collecting")
+        if steps_max is None:
+            steps_max = max(1, min(32, min(r.cap for r in replays) // m))
+        steps_max = int(steps_max)
+        if steps_max < 1:
+            raise ValueError(f"PopulationRollout: steps_max {steps_max} (>= 1)")
+        for p, r in enumerate(replays):
+            if steps_max * m > r.cap:
+                raise ValueError(f"PopulationRollout: member {p}: steps_max * m = {steps_max * m} > cap {r.cap}")
+        eps = [float(x) for x in _per_member("epsilon", epsilon, n)]
+        for p, x in enumerate(eps):
+            if not math.isfinite(x):
+                raise ValueError(f"PopulationRollout: member {p}: epsilon {x}")
+        mask = 0xFFFFFFFFFFFFFFFF
+        if seed_env is None:
+            seed_env = [env.seed + p for p in range(n)]
+        self.seed_env = [int(x) & mask for x in _per_member("seed_env", seed_env, n)]
+        self.seed_net = [int(x) & mask for x in _per_member("seed_net", seed_net, n)]
+        if not isinstance(params, torch.Tensor) or tuple(params.shape) != (n, PM_QNET_NP) or \
+                params.dtype != torch.float32 or not params.is_contiguous():
+            raise ValueError(f"PopulationRollout: params must be a contiguous float32 [n={n}, {PM_QNET_NP}] tensor "
+                             "(it is used in place)")
+        if isinstance(wA, (list, tuple)):  # one net per member; members given the same tensor read one copy
+            if len(wA) != n or not all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and
+                                       t.numel() == PM_QNET_NW for t in wA):
+                raise ValueError(f"PopulationRollout: wA as a list must hold n = {n} float32 [{PM_QNET_NW}] tensors")
+        elif not isinstance(wA, torch.Tensor) or wA.dtype != torch.float32 or \
+                wA.numel() not in (PM_QNET_NW, n * PM_QNET_NW):
+            raise ValueError(f"PopulationRollout: wA must hold {PM_QNET_NW} or n x {PM_QNET_NW} float32 values")
+        dev = torch.device(env.device)
+        if params.device.type != dev.type or (dev.index is not None and params.device.index != dev.index):
+            raise ValueError("PopulationRollout: params must be on the env's device")
+        # ---- nothing above allocates
+        self.lib = _lib.load()
+        self.env, self.n, self.m, self.steps_max = env, n, m, steps_max
+        self.params, self.replays, self.epsilon = params, replays, eps
+        dev = env.device
+        if isinstance(wA, (list, tuple)):
+            own = {id(t): _weights(t, PM_QNET_NW, "wA", dev) for t in wA}
+            self.wA = [own[id(t)] for t in wA]
+        else:
+            wA = wA.to(dev).reshape(-1, PM_QNET_NW).contiguous()
+            wA = wA.clone() if wA.data_ptr() % 16 else wA
+            self.wA = [wA[0 if wA.shape[0] == 1 else p] for p in range(n)]
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.wB = torch.zeros((n, PM_QNET_NW), **f32)  # the fold writes the images; their pads stay 0
+        self.heads = torch.empty((n, steps_max * PM_ROLL_HEADS), **f32)
+        self.ep_reward = torch.zeros(env.n, **f32)  # [n, m] flat: each arena's running episode
+        self.prio = torch.ones(n, **f32)  # the priority each member's last collect pushed
+        self.stats = torch.zeros((n, len(STATS_PUSH)), dtype=torch.int64, device=dev)
+        self._members = (_lib.RollMember * n)()
+        self._handle = None
+        self._advance = 0    # transitions every member pushed since the table was bound
+        self._left = None    # (pos, size) of every replay as the last collect left them
+        self._bufs = None    # the replays' buffers the table points into
+
+    def _fill_members(self):
+        for p, r in enumerate(self.replays):
+            mb = self._members[p]
+            mb.wA = self.wA[p].data_ptr()
+            mb.wB = self.wB[p].data_ptr()
+            mb.paramsB = self.params[p].data_ptr()
+            mb.heads_ws = self.heads[p].data_ptr()
+            mb.rp = _lib.RollReplay(trans=ptr(r.trans), prios=ptr(r.prios), per_work=ptr(r.work),
+                                    ep_reward=self.ep_reward[p * self.m:].data_ptr(), pos=r.pos, cap=r.cap, prio=1.0,
+                                    alpha=r.alpha)
+            mb.size = r.size
+            mb.prio_dev = self.prio[p:].data_ptr()
+            mb.stats = self.stats[p].data_ptr()
+            mb.epsilon = self.epsilon[p]
+            mb.seed_env, mb.seed_net = self.seed_env[p], self.seed_net[p]
+
+    def _bind(self, stream):
+        import ctypes
+        left = [(r.pos, r.size) for r in self.replays]
+        bufs = [(ptr(r.trans), ptr(r.prios), ptr(r.work), r.cap, r.alpha) for r in self.replays]
+        if self._handle is not None and left == self._left and bufs == self._bufs:
+            return
+        self._fill_members()
+        if self._handle is None:
+            h = ctypes.c_void_p()
+            check(self.lib.pm_rollout_pop_create(ctypes_ref(self.env.params), ctypes_ref(self.env.state), self._members,
+                                                 self.n, self.m, self.steps_max, ctypes.byref(h)), "pm_rollout_pop_create")
+            self._handle = h
+        else:
+            check(self.lib.pm_rollout_pop_rebind(self._handle, self._members, stream), "pm_rollout_pop_rebind")
+        self._advance, self._left, self._bufs = 0, left, bufs
+
+    def collect(self, steps, sync=True):
+        """`steps` vector steps of every member (0..steps_max). Returns the call's stats as a dict of STATS_PUSH
+        names to int64 arrays of n (reading them synchronises), or with sync=False the [n, 6] device tensor
+        (zeroed by the next collect)."""
+        steps = int(steps)
+        if not 0 <= steps <= self.steps_max:
+            raise ValueError(f"PopulationRollout.collect: steps {steps} (0..steps_max={self.steps_max})")
+        env, st = self.env, stream_ptr()
+        self.stats.zero_()
+        if steps:
+            self._bind(st)
+            check(self.lib.pm_qnet_fold(ptr(self.params), None, _lib.PM_FOLD_EVAL, 0, 0, None, ptr(self.wB), self.n, st),
+                  "pm_qnet_fold")
+            check(self.lib.pm_rollout_pop_push(self._handle, env.counter, steps, self._advance, ptr(env.obsA),
+                                               ptr(env.obsB), st), "pm_rollout_pop_push")
+            pushed = steps * self.m
+            self._advance += pushed
+            for r in self.replays:
+                r.advance(pushed)
+                r.max_prio_stale = True
+            self._left = [(r.pos, r.size) for r in self.replays]
+            env.counter += steps
+        if not sync:
+            return self.stats
+        host = self.stats.cpu().numpy()
+        return {name: host[:, k].copy() for k, name in enumerate(STATS_PUSH)}
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                self.lib.pm_rollout_pop_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
