@@ -489,12 +489,12 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqr_update_opt(const pm_dqn d, cons
     dqn_apply_body<true>(d, o, ak, nsq);
 }
 
-// One population member per workgroup: the record is block-uniform and comes in by scalar loads (pm_dqn_pop.h).
+// One population member per workgroup: the record is block-uniform and comes in by scalar loads (pop_member, pm_pop.h).
 __global__ __launch_bounds__(kDqn, 1) void k_dqp_update(const pm_dqn_member* tab, int gated) {
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
     __shared__ float ak[2];
     __shared__ double nsq[kDqn / 64];
-    const pm_dqn_member m = dqp_member(tab);
+    const pm_dqn_member m = pop_member(tab, blockIdx.x);
     if (gated && m.rp.idx[0] < 0) return;  // block-uniform: this member's update is void; the others' are not
     dqn_grads_body<true>(m.d, m.o, sm);
     __syncthreads();

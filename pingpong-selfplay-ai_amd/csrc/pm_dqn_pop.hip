@@ -1,71 +1,23 @@
 // K12 — a population of stand-alone DQN learners (pm_dqn_pop_*, include/pongmi.h): n independent members,
 // each a pm_dqn with its own pm_dqn_opt and, optionally, its own pm_dqn_replay, trained by one launch per
 // phase with a grid of n workgroups. This unit is host code: the handle, the validation (all of it before
-// the first HIP call, so a machine without a GPU reports the same codes), the aliasing rule and the device
-// table. The kernels are k_dqp_update (pm_dqn.hip) and k_dqp_sample / k_dqp_scatter (pm_dqn_replay.hip):
-// the solo kernels' bodies on tab[blockIdx.x].
+// the first HIP call, so a machine without a GPU reports the same codes) and the list of a member's writable
+// buffers; the device table and the aliasing rule are the shared layer's (pm_pop.h). The kernels are
+// k_dqp_update (pm_dqn.hip) and k_dqp_sample / k_dqp_scatter (pm_dqn_replay.hip): the solo kernels' bodies on
+// tab[blockIdx.x].
 //
 // Why no ordering between workgroups is needed: a member reads and writes its own buffers only (the
-// aliasing rule below makes that a checked fact), what two members may share is read-only during every
+// aliasing rule makes that a checked fact), what two members may share is read-only during every
 // launch, and the three phases of a replay update are separate launches on one stream, so member p's
 // sampler has finished before member p's update starts, as in the solo path. The only atomic is the
 // atomicOr on a member's own status word.
-#include <algorithm>
-#include <cstdarg>
-#include <cstdio>
-#include <vector>
-
 #include "pm_dqn_pop.h"
-
-extern "C" int64_t pm_per_work_bytes(int64_t cap);
 
 struct pm_dqn_pop {
     pm_dqn_member* tab;  // device, [n]
     int32_t n;
     int32_t has_replay;
 };
-
-namespace pm {
-
-// A failed per-member check: its message behind the member's index.
-int pop_member_fail(int rc, const char* who, int p) {
-    char msg[400];
-    snprintf(msg, sizeof(msg), "%s", pm_last_error());
-    return pm_fail(rc, "%s: member %d: %s", who, p, msg);
-}
-
-void pop_add(std::vector<PopRange>& v, int p, const char* kind, const void* ptr, size_t bytes) {
-    if (ptr && bytes) v.push_back(PopRange{(uintptr_t)ptr, (uintptr_t)ptr + bytes, p, kind});
-}
-
-// No writable byte range of one member may meet one of another's. Sorted by start, a range conflicts exactly
-// when it starts below the furthest end seen so far among the OTHER members' ranges: the furthest end overall
-// (top) and the furthest among members other than top's (other) are enough to know that.
-int pop_check_overlap(const char* who, std::vector<PopRange>& v) {
-    std::sort(v.begin(), v.end(), [](const PopRange& a, const PopRange& b) { return a.lo < b.lo; });
-    const PopRange* top = nullptr;
-    const PopRange* other = nullptr;
-    for (const PopRange& r : v) {
-        const PopRange* hit = nullptr;
-        if (top && top->member != r.member && r.lo < top->hi) hit = top;
-        else if (top && top->member == r.member && other && r.lo < other->hi) hit = other;
-        if (hit) {
-            const PopRange& a = hit->member < r.member ? *hit : r;
-            const PopRange& b = hit->member < r.member ? r : *hit;
-            return pm_fail(PM_E_ARG, "%s: member %d: its %s overlaps member %d's %s (writable buffers must be disjoint)", who,
-                           b.member, b.kind, a.member, a.kind);
-        }
-        if (!top || r.hi > top->hi) {
-            if (top && top->member != r.member && (!other || top->hi > other->hi)) other = top;
-            top = &r;
-        } else if (r.member != top->member && (!other || r.hi > other->hi)) {
-            other = &r;
-        }
-    }
-    return PM_OK;
-}
-
-}  // namespace pm
 
 namespace {
 
@@ -129,14 +81,8 @@ extern "C" int pm_dqn_pop_create(const pm_dqn* d, const pm_dqn_opt* opt, const p
     *out = nullptr;
     std::vector<pm_dqn_member> tab;
     if (int rc = build_table(who, d, opt, rp, n, tab)) return rc;
-    pm_dqn_member* dev = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, sizeof(pm_dqn_member) * (size_t)n);
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipMalloc: %s", who, hipGetErrorString(e));
-    e = hipMemcpy(dev, tab.data(), sizeof(pm_dqn_member) * (size_t)n, hipMemcpyHostToDevice);  // synchronous
-    if (e != hipSuccess) {
-        (void)hipFree(dev);
-        return pm_fail(PM_E_LAUNCH, "%s: hipMemcpy: %s", who, hipGetErrorString(e));
-    }
+    pm_dqn_member* dev;
+    if (int rc = pm::pop_table_create(who, tab.data(), sizeof(pm_dqn_member) * (size_t)n, (void**)&dev)) return rc;
     *out = new pm_dqn_pop{dev, n, rp ? 1 : 0};
     return PM_OK;
 }
@@ -147,11 +93,8 @@ extern "C" int pm_dqn_pop_rebind(pm_dqn_pop* pop, const pm_dqn* d, const pm_dqn_
     PM_REQUIRE(pop, PM_E_ARG, "%s: null handle", who);
     std::vector<pm_dqn_member> tab;
     if (int rc = build_table(who, d, opt, rp, pop->n, tab)) return rc;
-    // launches already on the stream read the old table: they finish before it is overwritten
-    hipError_t e = hipStreamSynchronize(pm_stream(stream));
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipStreamSynchronize: %s", who, hipGetErrorString(e));
-    e = hipMemcpy(pop->tab, tab.data(), sizeof(pm_dqn_member) * (size_t)pop->n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipMemcpy: %s", who, hipGetErrorString(e));
+    if (int rc = pm::pop_table_rebind(who, pop->tab, tab.data(), sizeof(pm_dqn_member) * (size_t)pop->n, pm_stream(stream)))
+        return rc;
     pop->has_replay = rp ? 1 : 0;
     return PM_OK;
 }
@@ -183,8 +126,7 @@ extern "C" int pm_dqn_pop_info(const pm_dqn_pop* pop, int32_t* n, int32_t* has_r
 
 extern "C" int pm_dqn_pop_destroy(pm_dqn_pop* pop) {
     PM_REQUIRE(pop, PM_E_ARG, "pm_dqn_pop_destroy: null handle");
-    hipError_t e = hipFree(pop->tab);
-    delete pop;
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "pm_dqn_pop_destroy: hipFree: %s", hipGetErrorString(e));
-    return PM_OK;
+    const int rc = pm::pop_table_free("pm_dqn_pop_destroy", pop->tab);
+    delete pop;  // even when hipFree failed
+    return rc;
 }

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void k_dqr_sample(const pm_dqn d, const pm_dqn
 // The population's draw + gather: workgroup p draws from member p's own tree into member p's own batch buffers.
 __global__ __launch_bounds__(256) void k_dqp_sample(const pm_dqn_member* tab, int upd) {
     __shared__ DqrSampleSmem sm;
-    const pm_dqn_member m = dqp_member(tab);
+    const pm_dqn_member m = pop_member(tab, blockIdx.x);
     const pm_dqn& d = m.d;
     const pm_dqn_replay& rp = m.rp;
 #include "pm_dqr_sample_body.inc"
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kScatter) void k_dqr_scatter(const pm_dqn d, const 
 // The population's scatter + tree refresh: member p's priorities and member p's tree only.
 __global__ __launch_bounds__(kScatter) void k_dqp_scatter(const pm_dqn_member* tab) {
     __shared__ int64_t sidx[PM_MAX_BATCH];
-    const pm_dqn_member m = dqp_member(tab);
+    const pm_dqn_member m = pop_member(tab, blockIdx.x);
     dqr_scatter_body(m.d, m.rp, sidx);
 }
 

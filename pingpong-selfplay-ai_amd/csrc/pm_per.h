@@ -231,6 +231,27 @@ __device__ __forceinline__ double per_chunk_sum(const PerTree& t, int64_t c) {
     return acc;
 }
 
+// Both node levels for one 256-thread block (blockIdx.x: its 64 level-1 nodes; subl: 64 doubles of LDS): the block
+// computes the nodes (four lanes each, per_sub_sum4) into HBM and LDS, then four of its threads sum their 16-node
+// groups into the level-2 nodes in per_chunk_sum's order (same values: the 16 loads per_chunk_sum would issue come
+// from LDS). Every thread of the block calls it.
+__device__ __forceinline__ void per_nodes_block(const PerTree& tr, const PushRange& pr, double* subl) {
+    const int64_t sb = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+    const double v = per_sub_sum4(tr.leaf, sb < tr.nsub ? sb : tr.nsub - 1, pr);
+    if ((threadIdx.x & 3) == 0) {
+        subl[threadIdx.x >> 2] = sb < tr.nsub ? v : 0.0;
+        if (sb < tr.nsub) tr.sub[sb] = v;
+    }
+    __syncthreads();
+    const int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x;
+    if (threadIdx.x < 4 && c < tr.nchunk) {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < PER_FAN; ++k) acc += subl[threadIdx.x * PER_FAN + k];
+        tr.chunk[c] = acc;
+    }
+}
+
 // ----------------------------------------------------------------------------- block sampler
 // PrioritizedReplay.sample (scripts/train_iterative.py:64-73): np.random.choice(p) picks the first
 // index whose running sum of p exceeds u (searchsorted 'right'). Here a 256-thread block draws

@@ -40,27 +40,12 @@ __global__ __launch_bounds__(256) void k_per_subs(int64_t cap, float alpha, cons
     }
 }
 
-// Both node levels in one launch: a block computes 64 level-1 nodes (four lanes each, as k_per_subs)
-// into HBM and LDS, then four of its threads sum their 16-node groups into the level-2 nodes in
-// per_chunk_sum's order (same values: the 16 loads per_chunk_sum would issue come from LDS).
+// Both node levels in one launch (per_nodes_block, pm_per.h), with the pending push range substituted.
 __global__ __launch_bounds__(256) void k_per_nodes(int64_t cap, float alpha, const pm_ctrl* ctrl, int64_t n_push,
                                                    PerTree tr) {
     __shared__ double subl[64];
     const PushRange pr = push_range(ctrl, n_push, cap, alpha);
-    const int64_t sb = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const double v = per_sub_sum4(tr.leaf, sb < tr.nsub ? sb : tr.nsub - 1, pr);
-    if ((threadIdx.x & 3) == 0) {
-        subl[threadIdx.x >> 2] = sb < tr.nsub ? v : 0.0;
-        if (sb < tr.nsub) tr.sub[sb] = v;
-    }
-    __syncthreads();
-    const int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x;
-    if (threadIdx.x < 4 && c < tr.nchunk) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < PER_FAN; ++k) acc += subl[threadIdx.x * PER_FAN + k];
-        tr.chunk[c] = acc;
-    }
+    per_nodes_block(tr, pr, subl);
 }
 
 __global__ __launch_bounds__(256) void k_per_chunks(PerTree tr) {

@@ -3,8 +3,8 @@
 //
 // A solo collecting rollout (pm_rollout_push) is three launches and, in Python, a fold and a 4-byte host read of
 // max(prios); a population of n members pays that n times per collect step, and a member's few hundred arenas
-// are a dozen blocks of a launch shaped for 65 536. Here the members' records sit in a device table (as
-// pm_dqn_pop's) and four launches serve all of them:
+// are a dozen blocks of a launch shaped for 65 536. Here the members' records sit in a device table (pm_pop.h,
+// as pm_dqn_pop's) and four launches serve all of them:
 //   k_rpp_prios  grid n: member p's pushed priority, max(prios[0:fill]) or 1.0f into an empty ring, written to
 //                prio_dev. A maximum has no order to keep, so it is the value DeviceReplay.push_prio() reads back
 //                on the host, taken where the priorities are (members without prio_dev push rp.prio);
@@ -26,15 +26,12 @@
 // paramsB) is read-only in every launch.
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
-#include "pm_dqn_pop.h"
 #include "pm_mfma.h"
 #include "pm_per.h"
+#include "pm_pop.h"
 
 using namespace pm;
-
-static_assert(sizeof(pm_roll_member) % 8 == 0 && alignof(pm_roll_member) == 8, "copied as 64-bit words");
 
 struct pm_rollout_pop {
     pm_roll_member* tab;  // device, [n]
@@ -48,20 +45,6 @@ struct pm_rollout_pop {
 namespace {
 
 #include "pm_rollout_push.inc"
-
-// Member p's record, read as dqp_member (pm_dqn_pop.h) reads its own: the table is written by the host only
-// and never during a launch, so it comes through the constant address space as block-uniform scalar loads.
-__device__ __forceinline__ pm_roll_member rpp_member(const pm_roll_member* tab, unsigned p) {
-    typedef const uint64_t __attribute__((address_space(4))) cword;
-    constexpr int kWords = sizeof(pm_roll_member) / 8;
-    cword* src = (cword*)(tab + p);
-    uint64_t w[kWords];
-#pragma unroll
-    for (int i = 0; i < kWords; ++i) w[i] = src[i];
-    pm_roll_member m;
-    __builtin_memcpy(&m, w, sizeof(m));
-    return m;
-}
 
 // The ring's fill and write slot `advance` transitions after the table was bound.
 __device__ __forceinline__ int64_t rpp_fill(const pm_roll_member& mb, int64_t advance) {
@@ -79,7 +62,7 @@ constexpr int kPriosBlock = 1024;
 __global__ __launch_bounds__(kPriosBlock) void k_rpp_prios(const pm_roll_member* tab, int64_t advance) {
     __shared__ float red[kPriosBlock / 64];
     __shared__ int bad[kPriosBlock / 64];
-    const pm_roll_member mb = rpp_member(tab, blockIdx.x);
+    const pm_roll_member mb = pop_member(tab, blockIdx.x);
     if (!mb.prio_dev) return;  // block-uniform
     const int64_t fill = rpp_fill(mb, advance);
     const float* __restrict__ prios = mb.rp.prios;
@@ -118,7 +101,7 @@ __global__ __launch_bounds__(kPriosBlock) void k_rpp_prios(const pm_roll_member*
 }
 
 __global__ __launch_bounds__(kHeadsBlock) void k_rpp_heads(const pm_roll_member* tab, uint64_t counter0) {
-    const pm_roll_member mb = rpp_member(tab, blockIdx.y);
+    const pm_roll_member mb = pop_member(tab, blockIdx.y);
     rollout_heads_body(mb.paramsB, mb.seed_net, counter0, mb.heads_ws, blockIdx.x);
 }
 
@@ -131,7 +114,7 @@ __global__ __launch_bounds__(kRollBlock) __attribute__((amdgpu_waves_per_eu(3, 3
     const pm_env_params p, const pm_env_state s, const pm_roll_member* __restrict__ tab, int m, int tiles,
     uint64_t counter0, int steps, int64_t advance, float* __restrict__ obsA, float* __restrict__ obsB) {
     const unsigned mem = blockIdx.x / (unsigned)tiles, tile = blockIdx.x - mem * (unsigned)tiles;
-    const pm_roll_member mb = rpp_member(tab, mem);
+    const pm_roll_member mb = pop_member(tab, mem);
     const size_t off = (size_t)mem * (size_t)m;  // the member's first arena
     const pm_env_state sl{s.x + off,   s.y + off,   s.vx + off,     s.vy + off,     s.spin + off,    s.top + off,
                           s.bot + off, s.scoreA + off, s.scoreB + off, s.bounces + off, nullptr};
@@ -148,29 +131,14 @@ __global__ __launch_bounds__(kRollBlock) __attribute__((amdgpu_waves_per_eu(3, 3
                       obsA + off * 7, obsB + off * 7, reinterpret_cast<long long*>(mb.stats), m, rp, (int)tile);
 }
 
-// k_per_nodes (pm_replay.hip) per member: 64 level-1 nodes per block, four lanes each (per_sub_sum4), then the
-// block's four level-2 nodes from LDS in per_chunk_sum's order. No pending push range: the leaves are written.
+// k_per_nodes (pm_replay.hip) per member, on the member's tree. No pending push range: the leaves are written.
 __global__ __launch_bounds__(256) void k_rpp_nodes(const pm_roll_member* tab) {
     __shared__ double subl[64];
-    const pm_roll_member mb = rpp_member(tab, blockIdx.y);
+    const pm_roll_member mb = pop_member(tab, blockIdx.y);
     if (!mb.rp.per_work) return;  // block-uniform, as the next
     const PerTree tr = per_tree(mb.rp.per_work, mb.rp.cap);
     if ((int64_t)blockIdx.x * 64 >= tr.nsub) return;
-    const PushRange pr{0, 0, mb.rp.cap, 0.f};
-    const int64_t sb = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const double v = per_sub_sum4(tr.leaf, sb < tr.nsub ? sb : tr.nsub - 1, pr);
-    if ((threadIdx.x & 3) == 0) {
-        subl[threadIdx.x >> 2] = sb < tr.nsub ? v : 0.0;
-        if (sb < tr.nsub) tr.sub[sb] = v;
-    }
-    __syncthreads();
-    const int64_t c = (int64_t)blockIdx.x * 4 + threadIdx.x;
-    if (threadIdx.x < 4 && c < tr.nchunk) {
-        double acc = 0.0;
-#pragma unroll
-        for (int k = 0; k < PER_FAN; ++k) acc += subl[threadIdx.x * PER_FAN + k];
-        tr.chunk[c] = acc;
-    }
+    per_nodes_block(tr, PushRange{0, 0, mb.rp.cap, 0.f}, subl);
 }
 
 // One member's record: everything pm_rollout_push rejects, for m arenas and launches of up to steps_max steps.
@@ -245,14 +213,8 @@ extern "C" int pm_rollout_pop_create(const pm_env_params* p, const pm_env_state*
     int32_t any_prio;
     int64_t node_blocks;
     if (int rc = check_table(who, members, n, m, steps_max, &any_prio, &node_blocks)) return rc;
-    pm_roll_member* dev = nullptr;
-    hipError_t e = hipMalloc((void**)&dev, sizeof(pm_roll_member) * (size_t)n);
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipMalloc: %s", who, hipGetErrorString(e));
-    e = hipMemcpy(dev, members, sizeof(pm_roll_member) * (size_t)n, hipMemcpyHostToDevice);  // synchronous
-    if (e != hipSuccess) {
-        (void)hipFree(dev);
-        return pm_fail(PM_E_LAUNCH, "%s: hipMemcpy: %s", who, hipGetErrorString(e));
-    }
+    pm_roll_member* dev;
+    if (int rc = pop_table_create(who, members, sizeof(pm_roll_member) * (size_t)n, (void**)&dev)) return rc;
     *out = new pm_rollout_pop{dev, *p, *s, n, m, steps_max, any_prio, node_blocks};
     return PM_OK;
 }
@@ -263,11 +225,8 @@ extern "C" int pm_rollout_pop_rebind(pm_rollout_pop* pop, const pm_roll_member* 
     int32_t any_prio;
     int64_t node_blocks;
     if (int rc = check_table(who, members, pop->n, pop->m, pop->steps_max, &any_prio, &node_blocks)) return rc;
-    // launches already on the stream read the old table: they finish before it is overwritten
-    hipError_t e = hipStreamSynchronize(pm_stream(stream));
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipStreamSynchronize: %s", who, hipGetErrorString(e));
-    e = hipMemcpy(pop->tab, members, sizeof(pm_roll_member) * (size_t)pop->n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "%s: hipMemcpy: %s", who, hipGetErrorString(e));
+    if (int rc = pop_table_rebind(who, pop->tab, members, sizeof(pm_roll_member) * (size_t)pop->n, pm_stream(stream)))
+        return rc;
     pop->any_prio = any_prio;
     pop->node_blocks = node_blocks;
     return PM_OK;
@@ -311,8 +270,7 @@ extern "C" int pm_rollout_pop_info(const pm_rollout_pop* pop, int32_t* n, int32_
 
 extern "C" int pm_rollout_pop_destroy(pm_rollout_pop* pop) {
     PM_REQUIRE(pop, PM_E_ARG, "pm_rollout_pop_destroy: null handle");
-    hipError_t e = hipFree(pop->tab);
-    delete pop;
-    if (e != hipSuccess) return pm_fail(PM_E_LAUNCH, "pm_rollout_pop_destroy: hipFree: %s", hipGetErrorString(e));
-    return PM_OK;
+    const int rc = pop_table_free("pm_rollout_pop_destroy", pop->tab);
+    delete pop;  // even when hipFree failed
+    return rc;
 }

@@ -34,6 +34,24 @@ ALL_SHAPES = [s for _, s in PARAM_LAYOUT[:12]]   # modelB.parameters() order
 HEAD_SHAPES = [s for _, s in PARAM_LAYOUT[4:12]]  # list(fc_V.parameters()) + list(fc_A.parameters()) (:101-104)
 
 
+def check_option(who, name, v):
+    """loss, huber_beta or max_norm as a learner keeps it, or ValueError in `who`'s name."""
+    if name == "loss":
+        if v not in ("mse", "huber"):
+            raise ValueError(f"{who}: loss {v!r} ('mse' or 'huber')")
+        return v
+    if name == "max_norm" and v is None:
+        return None
+    v = float(v)
+    if not (math.isfinite(v) and v > 0):  # huber_beta whichever loss: a bad value never waits for a switch
+        raise ValueError(f"{who}: {name} {v} " + ("(> 0, finite)" if name == "huber_beta" else "(None, or > 0 and finite)"))
+    return v
+
+
+BUFFERS = ("params", "target", "adam_m", "adam_v", "grad", "stats_buf", "s", "ns", "act", "rew", "done", "isw", "td", "q",
+           "idx")
+
+
 class DQNLearner:
     def __init__(self, modelB, target=None, *, batch=256, gamma=0.99, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8,
                  target_update_interval=1000, train_features=False, fresh_noise=True, seed=0, device="cuda",
@@ -45,38 +63,42 @@ class DQNLearner:
         clip_grad_norm_(the trained parameters, max_norm) between the gradient and Adam; stats() then
         also reports the total norm before the clip. With both at their defaults every call goes to the
         plain entry points."""
-        self.lib = _lib.load()
-        self.batch = int(batch)
-        if not 1 <= self.batch <= PM_MAX_BATCH:
-            raise ValueError(f"DQNLearner: batch {self.batch} (1..{PM_MAX_BATCH})")
-        if loss not in ("mse", "huber"):
-            raise ValueError(f"DQNLearner: loss {loss!r} ('mse' or 'huber')")
-        huber_beta = float(huber_beta)
-        if not (math.isfinite(huber_beta) and huber_beta > 0):  # whichever loss: a bad value never waits for a switch
-            raise ValueError(f"DQNLearner: huber_beta {huber_beta} (> 0, finite)")
-        if max_norm is not None:
-            max_norm = float(max_norm)
-            if not (math.isfinite(max_norm) and max_norm > 0):
-                raise ValueError(f"DQNLearner: max_norm {max_norm} (None, or > 0 and finite)")
-        self.loss, self.huber_beta, self.max_norm = loss, huber_beta, max_norm
+        lib = _lib.load()
+        batch = int(batch)
+        if not 1 <= batch <= PM_MAX_BATCH:
+            raise ValueError(f"DQNLearner: batch {batch} (1..{PM_MAX_BATCH})")
+        loss, huber_beta, max_norm = (check_option("DQNLearner", k, v) for k, v in
+                                      (("loss", loss), ("huber_beta", huber_beta), ("max_norm", max_norm)))
         self.device = torch.device(device)
-        self.train_features = bool(train_features)
-        self.params = self._block(modelB)
-        self.target = self._block(target) if target is not None else self.params.clone()
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.adam_m = torch.zeros(PM_DQN_NPARAM, **f32)
-        self.adam_v = torch.zeros(PM_DQN_NPARAM, **f32)
-        self.grad = torch.zeros(PM_DQN_NPARAM + 8, **f32)
-        self.stats_buf = torch.zeros(ctypes.sizeof(_lib.DqnStats), dtype=torch.uint8, device=self.device)
-        self.s = torch.zeros((self.batch, 7), **f32)
-        self.ns = torch.zeros((self.batch, 7), **f32)
-        self.act = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
-        self.rew = torch.zeros(self.batch, **f32)
-        self.done = torch.zeros(self.batch, dtype=torch.uint8, device=self.device)
-        self.isw = torch.ones(self.batch, **f32)
-        self.td = torch.zeros(self.batch, **f32)
-        self.q = torch.zeros((self.batch, 3), **f32)
-        self.idx = torch.zeros(self.batch, dtype=torch.int64, device=self.device)  # update_from's sampled slots
+        params = self._block(modelB)
+        z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self.device)  # noqa: E731
+        buffers = dict(
+            params=params, target=self._block(target) if target is not None else params.clone(),
+            adam_m=z(PM_DQN_NPARAM), adam_v=z(PM_DQN_NPARAM), grad=z(PM_DQN_NPARAM + 8),
+            stats_buf=z(ctypes.sizeof(_lib.DqnStats), dtype=torch.uint8), s=z(batch, 7), ns=z(batch, 7),
+            act=z(batch, dtype=torch.int32), rew=z(batch), done=z(batch, dtype=torch.uint8),
+            isw=torch.ones(batch, dtype=torch.float32, device=self.device), td=z(batch), q=z(batch, 3),
+            idx=z(batch, dtype=torch.int64))  # idx: update_from's sampled slots
+        norm = z(1) if max_norm is not None else None  # total norm before the clip of the last apply
+        self._attach(lib, self.device, buffers, norm, batch=batch, gamma=gamma, lr=lr, betas=betas, eps=eps,
+                     target_update_interval=target_update_interval, train_features=train_features,
+                     fresh_noise=fresh_noise, seed=seed, loss=loss, huber_beta=huber_beta, max_norm=max_norm)
+
+    @classmethod
+    def over(cls, lib, device, buffers, norm, **hyper):
+        """A learner over existing tensors (one per name in BUFFERS; norm: [1], given exactly when max_norm is) with
+        checked hyper-parameters: nothing is validated, allocated or copied. DQNPopulation.member() uses it."""
+        self = cls.__new__(cls)
+        self._attach(lib, device, buffers, norm, **hyper)
+        return self
+
+    def _attach(self, lib, device, buffers, norm, *, batch, gamma, lr, betas, eps, target_update_interval, train_features,
+                fresh_noise, seed, loss, huber_beta, max_norm):
+        """Everything a learner is, given its buffers: the attributes, the descriptor and the options."""
+        self.lib, self.device, self.batch = lib, device, batch
+        self.loss, self.huber_beta, self.max_norm, self.train_features = loss, huber_beta, max_norm, bool(train_features)
+        for name in BUFFERS:
+            setattr(self, name, buffers[name])
         d = _lib.Dqn()
         for name in ("params", "target", "adam_m", "adam_v", "grad", "s", "ns", "act", "rew", "done", "td", "q"):
             setattr(d, name, getattr(self, name).data_ptr())
@@ -91,14 +113,11 @@ class DQNLearner:
         d.seed_net = int(seed)
         self.desc = d
         # the options: None routes every call to the plain entry points, a pm_dqn_opt to the _opt ones
-        self.opt = None
-        self.norm = None
+        self.opt, self.norm = None, norm
         if loss != "mse" or max_norm is not None:
-            if max_norm is not None:
-                self.norm = torch.zeros(1, **f32)  # total norm before the clip of the last apply
             self.opt = _lib.DqnOpt(loss=_lib.PM_DQN_LOSS_HUBER if loss == "huber" else _lib.PM_DQN_LOSS_SQUARED,
                                    huber_beta=huber_beta, max_norm=max_norm if max_norm is not None else 0.0,
-                                   norm=self.norm.data_ptr() if self.norm is not None else None)
+                                   norm=norm.data_ptr() if norm is not None else None)
 
     def _block(self, m):
         if isinstance(m, torch.Tensor):

@@ -19,56 +19,28 @@ and the draw's arguments) and rebinds, the interface's only host synchronisation
 a loop over a fixed batch shape, or over full replays, never synchronises.
 """
 import ctypes
-import math
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import PM_DQN_NPARAM, PM_DQN_POP_MAX, PM_MAX_BATCH, PM_QNET_NP, check, stream_ptr
-from .dqn import DQNLearner
+from ._pop import TableHandle, per_member
+from .dqn import BUFFERS, DQNLearner, check_option
 from .qnet import fold, unpack_state_dict
 
 PER_MEMBER = ("gamma", "lr", "betas", "eps", "target_update_interval", "train_features", "fresh_noise", "seed", "loss",
               "huber_beta", "max_norm")
 _STATS_DTYPE = np.dtype([("steps", "<i8"), ("adam_t", "<i8"), ("loss", "<f4"), ("q_mean", "<f4"), ("status", "<i4"),
                          ("_pad", "<i4")])
-_SEQ = (list, tuple, np.ndarray, torch.Tensor)
-
-
-def _per_member(name, v, n):
-    """`v` as a list of n values: one value for all members, or a sequence of n."""
-    if name == "betas":
-        seq = isinstance(v, _SEQ) and len(v) > 0 and isinstance(v[0], _SEQ)
-        if not seq and not (isinstance(v, _SEQ) and len(v) == 2):
-            raise ValueError(f"DQNPopulation: betas {v!r} (a pair, or a sequence of n pairs)")
-    else:
-        seq = isinstance(v, _SEQ)
-    if not seq:
-        return [v] * n
-    if len(v) != n:
-        raise ValueError(f"DQNPopulation: {name} has {len(v)} values for {n} members")
-    return [x.item() if isinstance(x, (np.generic, torch.Tensor)) and name != "betas" else x for x in v]
+_per_member = partial(per_member, "DQNPopulation")
 
 
 def _validate(name, v):
     """One member's value of one hyper-parameter, as the descriptor stores it."""
-    if name == "loss":
-        if v not in ("mse", "huber"):
-            raise ValueError(f"DQNPopulation: loss {v!r} ('mse' or 'huber')")
-        return v
-    if name == "huber_beta":
-        v = float(v)
-        if not (math.isfinite(v) and v > 0):
-            raise ValueError(f"DQNPopulation: huber_beta {v} (> 0, finite)")
-        return v
-    if name == "max_norm":
-        if v is None:
-            return None
-        v = float(v)
-        if not (math.isfinite(v) and v > 0):
-            raise ValueError(f"DQNPopulation: max_norm {v} (None, or > 0 and finite)")
-        return v
+    if name in ("loss", "huber_beta", "max_norm"):
+        return check_option("DQNPopulation", name, v)
     if name == "betas":
         if len(v) != 2:
             raise ValueError(f"DQNPopulation: betas {v!r} (a pair)")
@@ -84,7 +56,9 @@ def _validate(name, v):
     return float(v)  # gamma, lr, eps
 
 
-class DQNPopulation:
+class DQNPopulation(TableHandle):
+    _entry = "pm_dqn_pop"
+
     def __init__(self, models, targets=None, *, n=None, batch=256, device="cuda", shared_batch=False, gamma=0.99,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, target_update_interval=1000, train_features=False,
                  fresh_noise=True, seed=0, loss="mse", huber_beta=1.0, max_norm=None):
@@ -117,7 +91,7 @@ class DQNPopulation:
         given = dict(gamma=gamma, lr=lr, betas=betas, eps=eps, target_update_interval=target_update_interval,
                      train_features=train_features, fresh_noise=fresh_noise, seed=seed, loss=loss, huber_beta=huber_beta,
                      max_norm=max_norm)
-        self.hyper = {k: [_validate(k, v) for v in _per_member(k, given[k], n)] for k in PER_MEMBER}
+        self.hyper = {k: [_validate(k, v) for v in _per_member(k, given[k], n, k == "betas")] for k in PER_MEMBER}
         # ---- nothing above allocates
         self.lib = _lib.load()
         self.n, self.shared_batch = n, bool(shared_batch)
@@ -155,7 +129,6 @@ class DQNPopulation:
             d.batch = self.batches[p]
             self._o[p].norm = self.norm[p:p + 1].data_ptr()
         self._write_hyper()
-        self._handle = None   # pm_dqn_pop*, created by the first update
         self._bound = None    # (bytes of _d, bytes of _o, bytes of the replay descriptors or None) the table holds
         self._rp = None       # the bound replay descriptors, kept across update() rebinds
         self._rp_key = None   # what _rp was built from
@@ -192,7 +165,7 @@ class DQNPopulation:
         for k, v in kw.items():
             if k not in PER_MEMBER:
                 raise ValueError(f"DQNPopulation: unknown hyper-parameter {k!r}")
-            new[k] = [_validate(k, x) for x in _per_member(k, v, self.n)]
+            new[k] = [_validate(k, x) for x in _per_member(k, v, self.n, k == "betas")]
         self.hyper.update(new)
         self._write_hyper()
 
@@ -240,12 +213,7 @@ class DQNPopulation:
     def _bind(self, rp, stream):
         """Make the device table hold (_d, _o, rp): create it, or rebind it if it holds something else."""
         want = (bytes(self._d), bytes(self._o), bytes(rp) if rp is not None else None)
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            check(self.lib.pm_dqn_pop_create(self._d, self._o, rp, self.n, ctypes.byref(h)), "pm_dqn_pop_create")
-            self._handle = h
-        elif want != self._bound:
-            check(self.lib.pm_dqn_pop_rebind(self._handle, self._d, self._o, rp, stream_ptr(stream)), "pm_dqn_pop_rebind")
+        self._table(want != self._bound, (self._d, self._o, rp, self.n), (self._d, self._o, rp, stream_ptr(stream)))
         self._bound = want
 
     def update(self, stream=None):
@@ -337,25 +305,15 @@ class DQNPopulation:
         i = int(i)
         if not 0 <= i < self.n:
             raise ValueError(f"DQNPopulation: member {i} (0..{self.n - 1})")
-        L = object.__new__(DQNLearner)
-        L.lib, L.batch, L.device = self.lib, self.batches[i], self.device
         h = {k: v[i] for k, v in self.hyper.items()}
-        L.loss, L.huber_beta, L.max_norm, L.train_features = h["loss"], h["huber_beta"], h["max_norm"], h["train_features"]
-        for name in ("params", "target", "adam_m", "adam_v", "grad", "stats_buf"):
-            setattr(L, name, getattr(self, name)[i])
-        for name in ("td", "q", "idx"):
-            setattr(L, name, getattr(self, name)[i][:L.batch])
-        for name in ("s", "ns", "act", "rew", "done", "isw"):
+        batch, buffers = self.batches[i], {}
+        for name in BUFFERS:
             t = getattr(self, name)
-            setattr(L, name, (t if self.shared_batch else t[i])[:L.batch])
-        L.desc = _lib.Dqn.from_buffer_copy(self._d[i])
-        L.norm, L.opt = None, None
-        if h["loss"] != "mse" or h["max_norm"] is not None:
-            L.opt = _lib.DqnOpt.from_buffer_copy(self._o[i])
-            if h["max_norm"] is not None:
-                L.norm = self.norm[i:i + 1]
-            else:
-                L.opt.norm = None
+            t = t if self.shared_batch and name in ("s", "ns", "act", "rew", "done", "isw") else t[i]
+            buffers[name] = t if name in ("params", "target", "adam_m", "adam_v", "grad", "stats_buf") else t[:batch]
+        L = DQNLearner.over(self.lib, self.device, buffers, self.norm[i:i + 1] if h["max_norm"] is not None else None,
+                            batch=batch, **h)
+        L.desc.isw, L.desc.batch = self._d[i].isw, self._d[i].batch  # as the table has them now
         return L
 
     # ------------------------------------------------------------------ population-based training
@@ -370,11 +328,3 @@ class DQNPopulation:
             t.copy_(t[src])
         counters = self.stats_buf.view(torch.int64)  # [n, 4]: steps, adam_t, (loss | q_mean), (status | pad)
         counters[:, :2] = counters[src, :2]
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                self.lib.pm_dqn_pop_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass

@@ -20,10 +20,13 @@ loop's memory.push((oB, aB, rB, nB, done)) (:242-243) — the rows go from regis
 the launch leaves the PER sum tree current — with ep_reward carried per arena (:245) and the stats
 gaining the loop's episode wins (ep_reward > 0, :247) and reward sum.
 """
+from functools import partial
+
 import torch
 
 from . import _lib
 from ._lib import PM_QNET_NP, PM_QNET_NW, PM_ROLL_HEADS, check, ptr, require_device, stream_ptr
+from ._pop import TableHandle, per_member
 from .env import ctypes_ref
 
 STATS = ("episodes", "wins_B", "points_A", "points_B")
@@ -112,17 +115,10 @@ def _weights(t, size, name, device):
     return t
 
 
-def _per_member(name, v, n):
-    """`v` as a list of n values: one value for all members, or a sequence of n (dqn_pop._per_member)."""
-    import numpy as np
-    if not isinstance(v, (list, tuple, np.ndarray, torch.Tensor)):
-        return [v] * n
-    if len(v) != n:
-        raise ValueError(f"PopulationRollout: {name} has {len(v)} values for {n} members")
-    return [x.item() if isinstance(x, (np.generic, torch.Tensor)) else x for x in v]
+_per_member = partial(per_member, "PopulationRollout")
 
 
-class PopulationRollout:
+class PopulationRollout(TableHandle):
     """The collecting rollout for a population (pm_rollout_pop_*, csrc/pm_rollout_pop.hip): n members of m arenas
     each, member p playing arenas [p * m, (p + 1) * m) of `env` against its own opponent and pushing into its
     own DeviceReplay, in one launch per phase instead of n solo rollouts. Member p's arenas, observations, ring,
@@ -147,6 +143,7 @@ class PopulationRollout:
     pos / size as of the last bind plus the transitions pushed since; it is rebound, the interface's only host
     synchronisation after the first collect, only when a replay's pos / size is not what this collector left
     (someone else pushed into it) or one of its buffers was replaced."""
+    _entry = "pm_rollout_pop"
 
     def __init__(self, env, wA, params, *, n, replays, epsilon=0.02, seed_env=None, seed_net=0, steps_max=None):
         import math
@@ -215,7 +212,6 @@ class PopulationRollout:
         self.prio = torch.ones(n, **f32)  # the priority each member's last collect pushed
         self.stats = torch.zeros((n, len(STATS_PUSH)), dtype=torch.int64, device=dev)
         self._members = (_lib.RollMember * n)()
-        self._handle = None
         self._advance = 0    # transitions every member pushed since the table was bound
         self._left = None    # (pos, size) of every replay as the last collect left them
         self._bufs = None    # the replays' buffers the table points into
@@ -237,19 +233,13 @@ class PopulationRollout:
             mb.seed_env, mb.seed_net = self.seed_env[p], self.seed_net[p]
 
     def _bind(self, stream):
-        import ctypes
         left = [(r.pos, r.size) for r in self.replays]
         bufs = [(ptr(r.trans), ptr(r.prios), ptr(r.work), r.cap, r.alpha) for r in self.replays]
         if self._handle is not None and left == self._left and bufs == self._bufs:
             return
         self._fill_members()
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            check(self.lib.pm_rollout_pop_create(ctypes_ref(self.env.params), ctypes_ref(self.env.state), self._members,
-                                                 self.n, self.m, self.steps_max, ctypes.byref(h)), "pm_rollout_pop_create")
-            self._handle = h
-        else:
-            check(self.lib.pm_rollout_pop_rebind(self._handle, self._members, stream), "pm_rollout_pop_rebind")
+        self._table(True, (ctypes_ref(self.env.params), ctypes_ref(self.env.state), self._members, self.n, self.m,
+                           self.steps_max), (self._members, stream))
         self._advance, self._left, self._bufs = 0, left, bufs
 
     def collect(self, steps, sync=True):
@@ -278,11 +268,3 @@ class PopulationRollout:
             return self.stats
         host = self.stats.cpu().numpy()
         return {name: host[:, k].copy() for k, name in enumerate(STATS_PUSH)}
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                self.lib.pm_rollout_pop_destroy(self._handle)
-                self._handle = None
-        except Exception:
-            pass
