@@ -234,6 +234,45 @@ int pm_play_rnn_rec(const pm_env_params* p, const float* w_qnet, int32_t n_qnet,
                     const int32_t* rec_row, int32_t n_rec, int32_t rec_cap, double* rec_f64, float* rec_q,
                     int32_t* rec_i32, void* stream);
 
+/* The league (csrc/pm_league.hip; additive to ABI 27: pm_sizeof unchanged, no struct): what stands around
+ * pm_play so that a population's fitness by greedy matches (the reference's eval_vs_model / eval_vs_pool,
+ * scripts/train_iterative.py:171-196, and its round-robin, tests/test_round_robin.py:290-330) and the
+ * truncation selection of population-based training are computed on the stream, with no host read. Every array
+ * is a caller-owned device pointer; every call only enqueues; arguments are checked on the host before the first
+ * HIP call. Integer sums only, no atomic, no workgroup waits for another.
+ *
+ *   pm_league_serves  serves[s] = the production serve of pm_env_reset (Philox(seed), counter (serve_idx[s],
+ *     round): speed, angle interval, angle, spin) for slots s in [0, m): bit for bit what pm_env_reset draws for
+ *     arena serve_idx[s] whose serve count is `round`. serves is [m][3] (vx, vy, spin) in slot order, as pm_play
+ *     takes it. m == 0 is a no-op. PM_E_SIZE: m < 0; PM_E_ARG: a null pointer, p->speed_scale_every <= 0.
+ *
+ *   pm_league_reduce  two launches, grid n_pairs then grid n_players. Pair k owns arenas [pair_first[k],
+ *     pair_first[k + 1]) of pm_play's per-arena outputs (pair_first holds n_pairs + 1 entries);
+ *     pair_stats[k][PM_LEAGUE_STATS] = games, wins_A, wins_B, draws, points_A, points_B, ticks, unfinished: an
+ *     arena with length < 0 counts in `unfinished` only; otherwise A wins when scoreA > scoreB, B when scoreB >
+ *     scoreA, else it is a draw, and ticks sums length. Player q's pairs are player_pairs[player_off[q] :
+ *     player_off[q + 1]] (player_off holds n_players + 1 entries), each entry 2 * pair + side (0 = the pair's A,
+ *     1 = its B; an entry naming no pair of [0, n_pairs) counts nowhere); player_stats[q][PM_LEAGUE_STATS] =
+ *     games, wins, losses, draws, points_for, points_against, ticks, unfinished summed over them;
+ *     fitness[q] = (float)wins / (float)games, 0.0f when games == 0. PM_E_SIZE: a negative count; PM_E_ARG: a
+ *     null pointer whose count is positive (player_pairs may be null while n_pairs == 0).
+ *
+ *   pm_pbt_select  one workgroup. f[p] = fitness[p], a NaN taken as -inf; member a is better than b iff f[a] >
+ *     f[b] || (f[a] == f[b] && a < b); rank[p] = the number of members better than p (a permutation of 0..n-1).
+ *     With r = Philox(seed), counter (p, purpose PBT, round): draw[p] = r.y for every p (for the caller's explore
+ *     step); a member with rank[p] >= n - n_bottom gets src_of[p] = the member of rank (r.x * n_top) >> 32, every
+ *     other member src_of[p] = p. PM_E_SIZE: n outside 1..PM_DQN_POP_MAX, n_bottom < 0, n_top < 1, n_bottom +
+ *     n_top > n; PM_E_ARG: a null pointer. */
+#define PM_LEAGUE_STATS 8
+int pm_league_serves(const pm_env_params* p, const int32_t* serve_idx, uint64_t seed, uint32_t round,
+                     double* serves, int32_t m, void* stream);
+int pm_league_reduce(const int32_t* scoreA, const int32_t* scoreB, const int32_t* length,
+                     const int32_t* pair_first, int32_t n_pairs,
+                     const int32_t* player_off, const int32_t* player_pairs, int32_t n_players,
+                     int64_t* pair_stats, int64_t* player_stats, float* fitness, void* stream);
+int pm_pbt_select(const float* fitness, int32_t n, int32_t n_bottom, int32_t n_top, uint64_t seed, uint64_t round,
+                  int32_t* rank, int64_t* src_of, uint32_t* draw, void* stream);
+
 /* K9 — inference-only self-play rollout, `steps` vector steps in one launch (BASELINE configs[1];
  * csrc/pm_rollout.hip). Replaces the act/step loop of scripts/train_iterative.py:239-242 with the
  * learner switched off: per vector step c = counter0 + s, modelB's heads are refolded with fresh

@@ -45,6 +45,7 @@ PM_GB_NONE, PM_GHEADS_LEN = 3, 264
 PM_TIMER_ACTENV, PM_TIMER_LEARN, PM_TIMER_RNN_ACT, PM_TIMER_ENV_STEP, PM_TIMER_ROLLOUT, PM_TIMER_DRQN = 0, 1, 2, 3, 4, 5
 PM_TIMER_LEARN_MULTI, PM_TIMER_N = 6, 7
 PM_ROLL_HEADS = 264
+PM_LEAGUE_STATS = 8
 
 
 class EnvParams(ctypes.Structure):
@@ -181,6 +182,10 @@ _SIGS = {
     "pm_play_rnn_rec": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                 c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_i32, c_i32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_league_serves": (c_i32, [c_void_p, c_void_p, c_u64, ctypes.c_uint32, c_void_p, c_i32, c_void_p]),
+    "pm_league_reduce": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "pm_pbt_select": (c_i32, [c_void_p, c_i32, c_i32, c_i32, c_u64, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pm_rollout": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64, c_u64, c_u64, c_i32,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_per_build": (c_i32, [c_void_p, c_i64, c_float, c_void_p, c_void_p]),
