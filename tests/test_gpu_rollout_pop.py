@@ -2,8 +2,14 @@
 pongmi.dqn.PopulationTrainer) on the MI355X: every member against a solo SelfPlayRollout.run(steps, replay=...) on
 its own PongEnv2PBatch(m, seed=seed_env[p]) whose state the member's slice was copied from. Everything is compared
 bit for bit, with no tolerance (the kernels are pure functions of their inputs): the ten state fields, obsA /
-obsB, ep_reward, the ring rows as int32, prios, the whole tree workspace (which in turn equals a fresh
-pm_per_build), pos / size and all six stats.
+obsB, ep_reward, the ring rows and prios as int32, the whole tree workspace (which in turn equals a fresh
+pm_per_build and the numpy model oracle.per_tree), pos / size and all six stats.
+
+Ring sizes: the rings bound here have at most 4000 entries, so k_rpp_prios runs one round with one real load
+per thread and k_rpp_nodes one block per member. Rings of 4096 to 65 536 entries (every load of every round of
+k_rpp_prios, its tail, unaligned and NaN paths, fill honoured and saturating, node grids of several and of
+unequal block counts, long chains of collects and a rebind on the device) are tests/test_gpu_rollout_pop_rings.py,
+on this file's Pair.
 
 Step counts: with random nets the CPU port (oracle/cpu_selfplay.py CpuRollout, seeds 0..5) ends its first
 episode after 14-19 vector steps at 32, 33 and 100 arenas, whatever epsilon, and after 16-101 steps at one arena.
@@ -36,8 +42,9 @@ def _params(n, seed):
     return (base.cpu() + 0.05 * torch.randn((n, base.shape[1]), generator=g)).cuda().contiguous()
 
 
-def _seed_ring(R, pos, size, seed, tree=True):
-    """A ring as a learner left it: `size` filled slots with priorities of its own, write slot `pos`."""
+def _seed_ring(R, pos, size, seed, tree=True, prepare=None):
+    """A ring as a learner left it: `size` filled slots with priorities of its own, write slot `pos`. prepare(R)
+    runs on the seeded ring before its tree and tracked maximum are taken (markers in prios)."""
     if not tree:
         R.work = None
     R.pos, R.size = pos, size
@@ -45,6 +52,8 @@ def _seed_ring(R, pos, size, seed, tree=True):
         g = torch.Generator().manual_seed(seed)
         R.prios[:size] = (torch.rand(size, generator=g) * 3 + 0.01).cuda()
         R.trans[:size] = torch.randn((size, 16), generator=g).cuda()
+    if prepare is not None:
+        prepare(R)
     _refresh(R)
 
 
@@ -64,11 +73,29 @@ def _tree_is_rebuild(R):
     assert torch.equal(R.work, w)
 
 
+def _tree_is_oracle(R):
+    """The workspace's chunk, sub and leaf sections against the numpy model of the tree (oracle.per_tree), which
+    shares no code with the library."""
+    import numpy as np
+    from oracle import oracle
+    from pongmi import replay as rp
+    cap = R.cap
+    chunk, sub, leaf = oracle.per_tree(R.prios.cpu().numpy(), cap, R.alpha)
+    work = R.work.cpu().numpy()
+    nchunk, nsub = -(-cap // 1024), -(-cap // 64)
+    o1 = rp._pad(nchunk)
+    o2 = o1 + rp._pad(nsub)
+    assert np.array_equal(work[:8 * nchunk].view(np.float64), chunk)
+    assert np.array_equal(work[o1:o1 + 8 * nsub].view(np.float64), sub)
+    assert np.array_equal(work[o2:o2 + 4 * cap].view(np.int32), leaf.view(np.int32))
+
+
 class Pair:
-    """A population collector and its n solo references on copies of the same state."""
+    """A population collector and its n solo references on copies of the same state. prepare(p, R) is called on
+    both of member p's rings once they are seeded, before their trees and tracked maxima are taken."""
 
     def __init__(self, n, m, caps, *, pos=0, size=0, eps=0.02, seed_env=None, seed_net=0, wA=None, steps_max, trees=None,
-                 unaligned=(), pop_seed=77):
+                 unaligned=(), pop_seed=77, prepare=None):
         from pongmi.env import PongEnv2PBatch
         from pongmi.replay import DeviceReplay
         from pongmi.rollout import PopulationRollout, SelfPlayRollout, _per_member
@@ -88,7 +115,8 @@ class Pair:
                 R.append(DeviceReplay(caps[p], "cuda"))
                 if p in unaligned:  # prios 4 bytes past a 16-byte boundary
                     R[-1].prios = torch.zeros(caps[p] + 1, device="cuda")[1:]
-                _seed_ring(R[-1], pos[p], size[p], 1000 + p, trees[p])
+                _seed_ring(R[-1], pos[p], size[p], 1000 + p, trees[p],
+                           prepare=None if prepare is None else (lambda ring, p=p: prepare(p, ring)))
             e = PongEnv2PBatch(m, seed=seed_env[p], autoreset=True)
             e.f64.copy_(self.env.f64[:, p * m:(p + 1) * m])
             e.i32.copy_(self.env.i32[:, p * m:(p + 1) * m])
@@ -124,10 +152,11 @@ class Pair:
             a, b = self.Rp[p], self.Rs[p]
             assert (a.pos, a.size) == (b.pos, b.size), p
             assert torch.equal(a.trans.view(torch.int32), b.trans.view(torch.int32)), p
-            assert torch.equal(a.prios, b.prios), p
+            assert torch.equal(a.prios.view(torch.int32), b.prios.view(torch.int32)), p  # bits: a NaN equals itself
             if a.work is not None:
                 assert torch.equal(a.work, b.work), p
                 _tree_is_rebuild(a)
+                _tree_is_oracle(a)
             assert e.counter == self.env.counter
         if not vacuous_ok:
             assert self.episodes > 0 and self.wrapped, (self.episodes, self.wrapped)

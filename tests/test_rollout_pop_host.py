@@ -338,3 +338,85 @@ def test_collect_calls_and_rebinds_only_when_someone_else_pushed(monkeypatch):
     one.lib = _Rec(_lib)
     one.collect(1)
     assert len({x.wA for x in one.lib.tables[-1]}) == 1
+
+
+# ----------------------------------------------------------------------------- the ring tables of the GPU tests
+# Mirrored from csrc/pm_rollout_pop.hip: k_rpp_prios runs kPriosBlock = 1024 threads per member, each with four
+# float4 loads per round (element e + k * kPriosBlock, clamped to e past the end) and a scalar tail; k_rpp_nodes
+# gives a block 64 level-1 nodes of PER_SUB = 64 leaves (csrc/pm_per.h).
+PRIOS_BLOCK, PRIOS_LOADS, BLOCK_NODES, NODE_LEAVES = 1024, 4, 64, 64
+
+
+def _prios_visits(fill, aligned):
+    """What k_rpp_prios does for one member: ({(round, k, clamped)} over all threads, entries left to the scalar loop)."""
+    n4 = fill // 4 if aligned else 0
+    loads = set()
+    for rnd, e0 in enumerate(range(0, n4, PRIOS_LOADS * PRIOS_BLOCK)):
+        for t in range(min(PRIOS_BLOCK, n4 - e0)):
+            loads |= {(rnd, k, e0 + t + k * PRIOS_BLOCK >= n4) for k in range(PRIOS_LOADS)}
+    return loads, fill - 4 * n4
+
+
+def _prios_reader(entry, fill, aligned):
+    """The load that reads `entry`: (round, k), or "tail" for the scalar loop."""
+    n4 = fill // 4 if aligned else 0
+    if entry >= 4 * n4:
+        return "tail"
+    per_round = PRIOS_LOADS * PRIOS_BLOCK
+    return entry // 4 // per_round, entry // 4 % per_round // PRIOS_BLOCK
+
+
+def _node_blocks(cap):
+    nsub = -(-cap // NODE_LEAVES)
+    return -(-nsub // BLOCK_NODES), nsub
+
+
+def test_ring_tables_reach_the_paths_they_claim():
+    """tests/test_gpu_rollout_pop_rings.py's member tables against a model of which loads k_rpp_prios issues and how
+    many blocks k_rpp_nodes gives a ring: fails when someone shrinks the rings back into the one-round, one-block
+    configuration."""
+    import test_gpu_rollout_pop_rings as rings
+    src = open(os.path.join(ROOT, "pingpong-selfplay-ai_amd", "csrc", "pm_rollout_pop.hip")).read()
+    for text in ("constexpr int kPriosBlock = 1024;", "e += 4 * kPriosBlock", "for (int k = 0; k < 4; ++k)",
+                 "e + k * kPriosBlock", "blockIdx.x * 64 >= tr.nsub"):
+        assert text in src, text  # the constants above are still the source's
+    tab = rings.PRIO_MEMBERS
+    where, tails, every = set(), set(), set()
+    for c in tab:
+        assert 0 < c["fill"] <= c["cap"] and all(0 <= e < c["fill"] for e, _ in c["marks"]), c
+        top = [e for e, v in c["marks"] if v != v] or [e for e, v in c["marks"] if v == rings.MARK]
+        assert len(top) == 1, c  # one entry decides the member's maximum: its NaN, else its one marker
+        loads, tail = _prios_visits(c["fill"], c["aligned"])
+        reader = _prios_reader(top[0], c["fill"], c["aligned"])
+        every |= loads
+        if reader == "tail":
+            assert top[0] == c["fill"] - 1  # the tail's last entry
+            tails.add((tail, c["aligned"]))
+        else:
+            assert (*reader, False) in loads
+            where.add(reader + (any(rnd == reader[0] and clamped for rnd, _, clamped in loads),))
+    # a maximum behind a real load at each k of the first round, and in each of four rounds
+    assert {(0, 0), (0, 1), (0, 2), (0, 3), (1, 0), (2, 2), (3, 3)} <= {w[:2] for w in where}
+    # ... behind a real k = 1 load of a round whose other k = 1 loads are clamped, and in a second round that has
+    # clamped loads at every k >= 1
+    assert (0, 1, True) in where and (1, 0, True) in where
+    assert {(1, k, True) for k in (1, 2, 3)} <= every and {(0, k, True) for k in (1, 2, 3)} <= every
+    # ... in tails of 1, 2 and 3 entries behind float4 rounds, and at the end of a many-pass unaligned loop
+    assert {(1, True), (2, True), (3, True)} <= tails
+    assert any(not a and t > 4 * PRIOS_BLOCK for t, a in tails)
+    assert any(v != v for c in tab for _, v in c["marks"])  # a NaN
+    assert all(2 * 32 <= c["cap"] for c in tab)
+
+    blocks = [_node_blocks(c["cap"]) for c in rings.NODE_MEMBERS if c["tree"]]
+    grid = max(b for b, _ in blocks)
+    assert grid == 16 and len({b for b, _ in blocks}) >= 3  # unequal across the launch's members
+    assert any(1 < b < grid for b, _ in blocks) and any(b == 1 for b, _ in blocks)  # members that leave blocks
+    assert any(b > 1 and nsub - BLOCK_NODES * (b - 1) == 1 and c["cap"] % NODE_LEAVES == 1
+               for (b, nsub), c in zip(blocks, (c for c in rings.NODE_MEMBERS if c["tree"])))  # one node, one leaf
+    assert (1, BLOCK_NODES) in blocks and any(b == 1 and nsub < BLOCK_NODES for b, nsub in blocks)
+    assert any(not c["tree"] for c in rings.NODE_MEMBERS)
+    assert all(30 * 33 <= c["cap"] for c in rings.NODE_MEMBERS)
+
+    chain = rings.CHAIN_MEMBERS
+    assert len({_node_blocks(c["cap"])[0] for c in chain}) == 3 and len({c["size"] / c["cap"] for c in chain}) == 3
+    assert 6 * 20 * 33 >= 3 * min(c["cap"] for c in chain) and all(20 * 33 <= c["cap"] for c in chain)
