@@ -273,6 +273,57 @@ int pm_league_reduce(const int32_t* scoreA, const int32_t* scoreB, const int32_t
 int pm_pbt_select(const float* fitness, int32_t n, int32_t n_bottom, int32_t n_top, uint64_t seed, uint64_t round,
                   int32_t* rank, int64_t* src_of, uint32_t* draw, void* stream);
 
+/* Matchmaking (csrc/pm_match.hip; additive to ABI 27 as the league is): after pm_league_reduce, every member's next
+ * training opponent drawn from its results and that opponent's net copied into the collector's table, and a
+ * Bradley-Terry rating of every player, each in one launch with no host read. pair_stats, player_off and
+ * player_pairs are pm_league_reduce's; pair_players is [n_pairs][2] = (player A, player B); net_of[q] is player q's
+ * row in the folded weight table w [n_nets][PM_QNET_NW], negative for a player without a net (the follower). Members
+ * are players 0..n-1. Arguments are checked on the host before the first HIP call. An entry of a pair list, the
+ * opponent it names and that opponent's net are range-checked before they index anything: no value in these
+ * arrays makes a kernel touch memory outside them (player_off is structure and must describe player_pairs).
+ *
+ *   pm_league_match  grid n, block 256. Entry e = 2 * pair + side of member p's list names the opponent o =
+ *     pair_players[pair][1 - side]; it is eligible iff 0 <= pair < n_pairs, 0 <= o < n_players, o != p and 0 <=
+ *     net_of[o] < n_nets. With g = the pair's games and s = 2 * (wins of p's side) + draws, in float32 with + - * /
+ *     only: x = g == 0 ? 0.5f : (float)s / (float)(2 * g); PM_MATCH_HARD: f = 1.0f multiplied `power` times by
+ *     (1.0f - x), one after the other (power 0 = uniform); PM_MATCH_EVEN: f = (4.0f * x) * (1.0f - x); the entry's
+ *     weight is q = (uint32_t)(f * 65535.0f) + 1, and 0 if it is not eligible. total[p] = the int32 sum of q;
+ *     t = (r.x * total) >> 32 with r = Philox(seed), counter (p, purpose MATCH = 11, round); opp[p] = the opponent of
+ *     the first entry in list order whose inclusive prefix sum exceeds t, and row net_of[opp[p]] of w is copied into
+ *     row p of wA_out [n][PM_QNET_NW]. total[p] == 0: opp[p] = -1 and row p of wA_out is not written. A list holds
+ *     at most PM_LEAGUE_MATCH_MAX entries (the sum then fits int32); the entry point cannot see the lists, so the
+ *     caller checks that (pongmi.matchmaking.Matchmaker does), and the kernel looks at no entry past that many.
+ *     PM_E_SIZE: n outside 1..PM_DQN_POP_MAX, n_players < n, n_pairs < 0, n_nets < 1, an unknown mode, power
+ *     outside 0..PM_MATCH_POWER_MAX. PM_E_ARG: a null buffer (pair_stats, pair_players and player_pairs may be null
+ *     while n_pairs == 0), w or wA_out not 16-byte aligned, another buffer not aligned to its element, wA_out
+ *     [n rows] overlapping w [n_nets rows]. There is no no-op size.
+ *
+ *   pm_league_rate  one workgroup of 1024. An entry of player q's list counts iff 0 <= pair < n_pairs, 0 <= o <
+ *     n_players, o != q and g > 0. W_q = 0.5f * (float)S_q + 0.5f * prior with S_q the int64 sum of s over them;
+ *     r = 1.0f to begin with; each of `iterations` Jacobi steps sets r'_q = W_q / D_q, D_q = prior / (r_q + 1.0f) +
+ *     sum over the entries of (float)g / (r_q + r_o): the prior is `prior` games against a virtual player of strength
+ *     1, half of them won, which keeps an unbeaten player finite and fixes the scale (nothing is normalised).
+ *     rating[q] = r_q after the last step. The order of the float32 additions is fixed: lane l of the player's wave
+ *     adds the entries at list positions l, l + 64, ... in that order onto 0.0f, the 64 lane sums combine pairwise
+ *     over adjacent blocks of 2, 4, 8 and 16 lanes and then as (row 0 + row 1) + (row 2 + row 3), and the prior's
+ *     term is added to that from the left (csrc/pm_match.hip's header; pongmi.matchmaking.rate_host restates it bit
+ *     for bit). n_players == 0 is a no-op. PM_E_SIZE: n_players outside 0..PM_LEAGUE_RATE_MAX (the strengths live in
+ *     LDS twice, beside W), n_pairs < 0, iterations outside 0..PM_LEAGUE_RATE_ITER_MAX. PM_E_ARG: prior not
+ *     positive and finite, a null buffer (as above), a buffer not aligned to its element. */
+#define PM_MATCH_HARD 0
+#define PM_MATCH_EVEN 1
+#define PM_MATCH_POWER_MAX 8
+#define PM_LEAGUE_MATCH_MAX 32767
+#define PM_LEAGUE_RATE_MAX 4096
+#define PM_LEAGUE_RATE_ITER_MAX 4096
+int pm_league_match(const int64_t* pair_stats, const int32_t* pair_players, int32_t n_pairs,
+                    const int32_t* player_off, const int32_t* player_pairs, int32_t n_players,
+                    const int32_t* net_of, const float* w, int32_t n_nets, int32_t n, int32_t mode, int32_t power,
+                    uint64_t seed, uint64_t round, float* wA_out, int32_t* opp, int32_t* total, void* stream);
+int pm_league_rate(const int64_t* pair_stats, const int32_t* pair_players, int32_t n_pairs,
+                   const int32_t* player_off, const int32_t* player_pairs, int32_t n_players,
+                   int32_t iterations, float prior, float* rating, void* stream);
+
 /* K9 — inference-only self-play rollout, `steps` vector steps in one launch (BASELINE configs[1];
  * csrc/pm_rollout.hip). Replaces the act/step loop of scripts/train_iterative.py:239-242 with the
  * learner switched off: per vector step c = counter0 + s, modelB's heads are refolded with fresh

@@ -158,7 +158,7 @@ __device__ __forceinline__ int wave_incl_scan_i32(int v) {
 
 // ----------------------------------------------------------------------------- RNG
 enum : uint32_t { TAG_SERVE = 1, TAG_ACT = 2, TAG_OPP = 3, TAG_NOISE_ACT = 4, TAG_PER = 5, TAG_NOISE_TRAIN = 6, TAG_NOISE_RNN = 7, TAG_SEQ = 8,
-                  TAG_SERVE_STEP = 9, TAG_PBT = 10 };
+                  TAG_SERVE_STEP = 9, TAG_PBT = 10, TAG_MATCH = 11 };
 
 struct U4 {
     uint32_t x, y, z, w;

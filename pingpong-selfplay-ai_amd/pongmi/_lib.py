@@ -46,6 +46,9 @@ PM_TIMER_ACTENV, PM_TIMER_LEARN, PM_TIMER_RNN_ACT, PM_TIMER_ENV_STEP, PM_TIMER_R
 PM_TIMER_LEARN_MULTI, PM_TIMER_N = 6, 7
 PM_ROLL_HEADS = 264
 PM_LEAGUE_STATS = 8
+PM_MATCH_HARD, PM_MATCH_EVEN, PM_MATCH_POWER_MAX = 0, 1, 8
+PM_LEAGUE_MATCH_MAX = 32767
+PM_LEAGUE_RATE_MAX = 4096
 
 
 class EnvParams(ctypes.Structure):
@@ -186,6 +189,10 @@ _SIGS = {
     "pm_league_reduce": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),
     "pm_pbt_select": (c_i32, [c_void_p, c_i32, c_i32, c_i32, c_u64, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_league_match": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32,
+                                c_i32, c_i32, c_u64, c_u64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_league_rate": (c_i32, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_i32, c_i32, c_float, c_void_p,
+                               c_void_p]),
     "pm_rollout": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64, c_u64, c_u64, c_i32,
                            c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_per_build": (c_i32, [c_void_p, c_i64, c_float, c_void_p, c_void_p]),

@@ -128,7 +128,11 @@ class PopulationRollout(TableHandle):
     env       a PongEnv2PBatch of n * m arenas, autoreset, no serve table. Its counter is every member's Philox
               step counter; its seed is only the default of seed_env.
     wA        the opponents' effective weights: one [PM_QNET_NW] net for all members, [n, PM_QNET_NW], or a list
-              of n [PM_QNET_NW] tensors (members given the same tensor read the one copy).
+              of n [PM_QNET_NW] tensors (members given the same tensor read the one copy). A contiguous, 16-byte
+              aligned float32 [n, PM_QNET_NW] tensor on the env's device is PLAYED IN PLACE: the member table holds
+              pointers to its rows (self.wA[p] is a view of row p), so whoever rewrites a row on the stream, such
+              as pongmi.matchmaking.Matchmaker.assign on its `wA`, changes the opponent from the next collect on,
+              with no call here (tests/test_gpu_match.py pins the row addresses).
     params    the members' stacked [n, PM_QNET_NP] modelB blocks, USED IN PLACE (contiguous float32 on the env's
               device): pass DQNPopulation.params and every collect plays what the learners hold, with no copy.
     replays   n distinct DeviceReplays, cap >= steps_max * m each; one whose `work` is None keeps no sum tree.
