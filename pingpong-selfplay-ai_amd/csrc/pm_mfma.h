@@ -134,16 +134,60 @@ __device__ __forceinline__ void stage_frags_lds(const float* __restrict__ w, flo
 // opponent tiles read their rows with two small loads instead of compacting ids next to MFMA waves
 // (VALU there waits for the matrix cores). Block-wide (kListBlock threads); more than kListNets
 // nets: no lists (the act kernel compacts).
+//
+// Up to kListPacked nets (the workload's pool of 8 is 9) the grouping is one packed scan: a lane's
+// one-hot of its net is a byte field (a wave's sum of a field reaches 64: 7 bits at the least) of four
+// words, and one inclusive wave scan per word gives every lane its rank inside its net (its own
+// field, less one) and lane 63 the wave's count of every net. The four waves' totals cross LDS once;
+// behind that one barrier lane k of every 16-lane row widens net k's four fields (a block's sum
+// reaches 256), adds them and scans the nets inside its row, so every wave forms its own offsets and
+// a lane fetches its net's from lane `net`. The ballot loop below took a round of compare, ballot,
+// popcount and lane-0 LDS store per net, then a wave-0 serial pass between two barriers.
 constexpr int kListNets = 64;
 constexpr int kListBlock = 256;
-struct OppListSmem {
-    int woff[kListBlock / 64][kListNets];  // per-wave count, then per-wave offset within the net
+constexpr int kListPacked = 16;
+struct alignas(16) OppListSmem {
+    union {
+        int woff[kListBlock / 64][kListNets];  // per-wave count, then per-wave offset within the net
+        int wtot[kListPacked / 4][kListBlock / 64];  // packed path: word j of wave w's byte-field totals
+    };
     int noff[kListNets], ncnt[kListNets];
 };
 __device__ __forceinline__ void write_opp_lists(int nn, int32_t* opp_list, int32_t* opp_cnt, OppListSmem& sm, int blk,
                                                 int i, bool valid, int net) {
     if (nn > kListNets) return;  // uniform
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (nn <= kListPacked) {  // uniform
+        static_assert(kListBlock / 64 == 4 && kListPacked == 16, "four waves' totals as one int4, nets 0-15 in a row");
+        const bool m = valid && (unsigned)net < (unsigned)nn;
+        const int sh = 8 * (net & 3), wsel = net >> 2;
+        const int one = m ? 1 << sh : 0;
+        int s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = wave_incl_scan_i32(wsel == j ? one : 0);
+        if (lane == 63) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sm.wtot[j][wv] = s[j];
+        }
+        const int mine = wsel == 0 ? s[0] : (wsel == 1 ? s[1] : (wsel == 2 ? s[2] : s[3]));
+        const int rank = ((mine >> sh) & 255) - 1;
+        __syncthreads();
+        const int k = lane & 15, ks = 8 * (k & 3);
+        const int4 t = *reinterpret_cast<const int4*>(sm.wtot[k >> 2]);
+        const int c0 = (t.x >> ks) & 255, c1 = (t.y >> ks) & 255, c2 = (t.z >> ks) & 255, c3 = (t.w >> ks) & 255;
+        const int cnt = (c0 + c1) + (c2 + c3);
+        const int pre = wv == 0 ? 0 : (wv == 1 ? c0 : (wv == 2 ? c0 + c1 : c0 + c1 + c2));  // the waves before this one
+        int inc = cnt;  // inclusive scan over the row's 16 nets (row_shr, zeros shifted in)
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);
+        inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);
+        const int noff = inc - cnt;
+        const int base = __shfl(noff + pre, net & (kListPacked - 1));  // lane k < 16 holds net k's
+        if (m) opp_list[(size_t)blk * kListBlock + base + rank] = i;
+        if ((int)threadIdx.x < nn) opp_cnt[(size_t)blk * nn + threadIdx.x] = (noff << 16) | cnt;
+        return;
+    }
     int rank = 0;
     for (int k = 0; k < nn; ++k) {
         const bool m = valid && net == k;

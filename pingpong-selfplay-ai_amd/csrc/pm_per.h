@@ -384,17 +384,23 @@ __device__ __forceinline__ int per_group_find(const double (&v)[NV], double x, d
 struct NoHook {
     __device__ void operator()() const {}
 };
-// l2done(): called by every thread once the level-2 search is done (before the level-1 loads), where
-// a caller issues work whose loads must not delay the chunk-sum round trip.
+// l1issued() / l0issued(): called by every thread right behind the issue of the level-1 (sub sum) and
+// of the level-0 (leaf) loads, where a caller issues loads of its own that must delay neither the
+// chunk-sum round trip nor the descent: vmcnt retires in issue order, so a load issued in front of the
+// sub sums is waited for with them. Plain loads go into l1issued (the sub sums' wait then counts them
+// out); LDS DMA goes into l0issued, behind the last loads of the descent (with LDS DMA in flight hipcc
+// waits vmcnt(0) at the next use of a plain load, and the leaves are the last such use). Nothing may
+// be consumed inside a hook.
 // RAW: out(j, idx, pa, total) instead, the leaf and the total the weight is formed from: the fp64 pow
 // (~300 instructions and two divisions) then no longer stands between the leaf search and whatever
 // the caller does with idx. The caller evaluates per_is_weight(size, pa, total, beta) itself.
 __device__ __forceinline__ float per_is_weight(int64_t size, double pa, double total, double beta) {
     return (float)pow((double)size * (pa / total), -beta);
 }
-template <bool RAW = false, class UFn, class OutFn, class Hook = NoHook>
+template <bool RAW = false, class UFn, class OutFn, class Hook1 = NoHook, class Hook0 = NoHook>
 __device__ inline void per_sample_block(bool active, int64_t size, const PerTree& tr, const PushRange& pr, double beta,
-                                        int j0, int bs, PerSampleSmem& sm, UFn ufn, OutFn out, Hook l2done = Hook()) {
+                                        int j0, int bs, PerSampleSmem& sm, UFn ufn, OutFn out, Hook1 l1issued = Hook1(),
+                                        Hook0 l0issued = Hook0()) {
     const int t = threadIdx.x, q = t & 3;
     const int j = j0 + (t >> 2);
     const bool one_round = tr.nchunk <= PER_ROUND;  // kernel-argument uniform
@@ -457,12 +463,14 @@ __device__ inline void per_sample_block(bool active, int64_t size, const PerTree
     }
     if (blk < 0) { blk = lastnz; before = lastbef; }
     PM_BLK(4);
-    l2done();
     // level 1: the chunk's 16 sub sums, 4 per lane of the sample's group
     double sv[4];
     const int64_t s0 = blk * PER_FAN + 4 * q;
 #pragma unroll
     for (int e = 0; e < 4; ++e) sv[e] = s0 + e < tr.nsub ? tr.sub[s0 + e] : 0.0;
+    __builtin_amdgcn_sched_barrier(0);
+    l1issued();
+    __builtin_amdgcn_sched_barrier(0);
     double b1, v1;
     const int64_t sb = blk * PER_FAN + per_group_find<4>(sv, x - before, b1, v1);
     PM_BLK(5);
@@ -482,6 +490,9 @@ __device__ inline void per_sample_block(bool active, int64_t size, const PerTree
 #pragma unroll
             for (int k = 0; k < 16; ++k) f[k] = lo + k < pr.cap ? tr.leaf[lo + k] : 0.f;
         }
+        __builtin_amdgcn_sched_barrier(0);
+        l0issued();
+        __builtin_amdgcn_sched_barrier(0);
         // covers(lo + k) and lo + k < size as ranges of k, one set per lane, instead of a ring distance
         // and a 64-bit compare per leaf: leaf k lies d0 + k into the ring from pos while k < kw (the
         // ring's wrap), k - kw after it, and is in the push range when that is below n.

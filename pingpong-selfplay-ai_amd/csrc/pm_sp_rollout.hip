@@ -26,7 +26,18 @@ static __device__ unsigned long long pm_diag_env[8][1024];
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                            \
         if (threadIdx.x == 0 && (blk) < 1024) pm_diag_env[(k)][(blk)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
+// where the env block runs, as PM_BLK_END's slot 3: CU id (__smid) | XCC id << 16, read at the block's start
+static __device__ unsigned long long pm_diag_env_place[1024];
+#define PM_ENV_PLACE(blk)                                                                      \
+    do {                                                                                       \
+        if (threadIdx.x == 0 && (blk) < 1024)                                                  \
+            pm_diag_env_place[(blk)] =                                                         \
+                (unsigned long long)__smid() | ((unsigned long long)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 15) << 16); \
+    } while (0)
 #else
+#define PM_ENV_PLACE(blk) \
+    do {                  \
+    } while (0)
 #define PM_ENV_STAMP(k, blk) \
     do {                     \
     } while (0)
@@ -198,11 +209,13 @@ __device__ __forceinline__ void sample_fwd_block16(const pm_selfplay& sp, int b,
     // (t = i >> 3, rq = (i & 7) >> 1) of the same row and lane half. So a wave loads 9 float4s whose
     // lanes form two 256-byte runs each (36 cache lines; gathering the 18 floats from the plain weights
     // touched 16 lines per load and held the level-1 loads behind it back by 1.3 us), plus the b2 quad
-    // its accumulator starts from. They and the LDS DMA of the two head sets are issued once the top
-    // level of the descent is done: in front of the chunk sums they would stand in their round trip
-    // (with LDS DMA in flight hipcc waits vmcnt(0) at the next use of a plain load). Nothing here is
-    // consumed before the level-1 loads are: a load used inside the hook would hold its wave for a round
-    // trip of its own.
+    // its accumulator starts from. They are issued right behind the level-1 (sub sum) loads and the LDS
+    // DMA of the two head sets right behind the leaf loads (pm_per.h l1issued / l0issued): in front of
+    // the chunk sums they would stand in that round trip, and in front of the sub sums, where they stood
+    // before, the sub sums' wait counted all ten of them (vmcnt retires in issue order; level 2 -> level 1
+    // 1.08 -> 0.76 us). With LDS DMA in flight hipcc waits vmcnt(0) at the next use of a plain load, so
+    // the DMA goes behind the descent's last loads. Nothing here is consumed inside a hook: a load used
+    // there would hold its wave for a round trip of its own.
     float4 f1 = make_float4(0.f, 0.f, 0.f, 0.f), f2[8], b2r = f1;
 #pragma unroll
     for (int m = 0; m < 8; ++m) f2[m] = f1;
@@ -227,8 +240,8 @@ __device__ __forceinline__ void sample_fwd_block16(const pm_selfplay& sp, int b,
 #pragma unroll
             for (int m = 0; m < 8; ++m) f2[m] = q2[m * 64];
             b2r = *reinterpret_cast<const float4*>(w + B2 + 16 * rt + 4 * g);
-            copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf);
-        });
+        },
+        [&] { copy_lds_f32x4<2 * 264>(sp.learn_heads, sm.hf); });
     if (!active) return;  // block-uniform
     __syncthreads();  // sidx, the staged heads
     PM_BLK(1);
@@ -375,6 +388,7 @@ __device__ __forceinline__ void env_block(const pm_selfplay& sp, int blk, EnvSme
     const pm_ctrl* c = sp.ctrl;
     if (blk == 0) PM_STAMP_ANY(72);
     PM_ENV_STAMP(0, blk);
+    PM_ENV_PLACE(blk);
     float xs[2][4];
     f32x16 fc2[2][2];  // featB: this wave's two tiles of modelB's features (computed ahead)
     // actions ahead: gB holds the greedy action (or, tile-wise, the sentinel). Nothing is staged and
@@ -711,5 +725,8 @@ extern "C" int pm_diag_read_blk(uint64_t* out) {  // k_act_sp's blocks / k_acten
 }
 extern "C" int pm_diag_read_env(uint64_t* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pm_diag_env), sizeof(uint64_t) * 8 * 1024);
+}
+extern "C" int pm_diag_read_env_place(uint64_t* out) {  // the env blocks' CU | XCC << 16
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pm_diag_env_place), sizeof(uint64_t) * 1024);
 }
 #endif
