@@ -713,6 +713,68 @@ int pm_replay_push(float* trans, float* prios, void* per_work, int64_t cap, int6
                    const float* s, const int32_t* act, const float* rew, const float* ns, const uint8_t* done,
                    int32_t n, void* stream);
 
+/* ---------------------------------------------------------------- n-step returns (additive to ABI 27) */
+
+/* Multi-step targets for the stand-alone stack: pm_sizeof and every struct above are unchanged; new entry
+ * points beside the old ones, which compute what they computed.
+ * Row format. A replay row's horizon k (1..PM_NSTEP_MAX) is stored as k - 1 in bits 16..18 of the row's last
+ * word, beside a | done << 8; the other bits stay as they are and readers mask with 7, so every bit pattern is a
+ * valid horizon and every row written by pm_rollout_push / pm_replay_push decodes as one step. A ring may mix
+ * horizons.
+ * Discount. With g = (float)gamma: disc(1) = g, disc(k) = disc(k - 1) * g (float32 products in that order, no
+ * fma). A row of horizon k has the target t = R + (disc(k) * nq) * (done ? 0 : 1): pm_dqn_update's for k = 1.
+ * N-step reward. A pending transition keeps float32 (R, f), (0, 1) when it is opened; each tick with B's reward
+ * r does R = R + f * r (a multiply, then an add), f = f * g, k += 1.
+ *
+ *   pm_dqn_nstep  horizon: device [d->batch] bytes, row j's horizon read as ((h - 1) & 7) + 1. pm_dqn_grads_n /
+ *     pm_dqn_update_n are pm_dqn_grads_opt / pm_dqn_update_opt (opt nullable as there) with row j's target
+ *     discounted by disc(horizon[j]); rows with done = 1 ignore it. A null pm_dqn_nstep or a null horizon IS the
+ *     _opt entry: the same launch, bit for bit. The apply step has no horizon (pm_dqn_apply_opt).
+ *   pm_dqn_replay_update_n  pm_dqn_replay_update_opt whose gather also decodes each sampled row's horizon into
+ *     horizon[j], next to act and done, and whose update reads it there. PM_E_ARG: a null nstep or horizon.
+ *   pm_dqn_nstep_pop_set  attaches horizon buffers to a population: nstep is a HOST array of n entries (a null
+ *     array, or all-null horizons, detaches them), member p's update then being pm_dqn_update_n's and its replay
+ *     update pm_dqn_replay_update_n's; members with a null horizon keep the one-step target. As
+ *     pm_dqn_pop_rebind it validates on the host first and then waits for `stream`; the horizon buffers ([batch]
+ *     bytes) join the aliasing rule, here and in every later rebind (PM_E_ARG, naming both members).
+ *   pm_rollout_push_n  pm_rollout_push with a window of nstep ticks and g = (float)gamma. At step st arena i
+ *     opens a pending transition (s = obsB before the step, aB); then every pending transition of the arena,
+ *     the new one included, takes the tick's rB as above. If the tick ended the episode all of them are written
+ *     with s' = the terminal observation, done = 1 and their own k and R, and the window is empty; otherwise the
+ *     one that has reached k = nstep is written with s' = the observation after the tick and done = 0. After the
+ *     launch's last step every transition still pending is written the same way with its shorter k and done = 0:
+ *     nothing is carried between launches, and a shorter horizon is still a correct target because the row
+ *     says which it has. The transition opened at step st goes to slot (pos + st * n + i) mod cap, so ring
+ *     accounting, steps * n <= cap, the pushed priority, the PER leaves and the tree rebuild are
+ *     pm_rollout_push's, every slot of the range is written once before the nodes are rebuilt, and the
+ *     trajectory (actions, env state, observations), ep_reward and the six stats do not depend on nstep.
+ *     nstep = 1 is pm_rollout_push: the same launch, bit for bit.
+ *   pm_rollout_nstep_pop_set  member p of pm_rollout_pop_push collects as pm_rollout_push_n(nstep[p],
+ *     gamma[p]): HOST arrays of n (both null: every member one step again). Validates on the host, then waits
+ *     for `stream` where horizons were set before.
+ *   pm_replay_push_n  pm_replay_push with row i's horizon (horizon[i] - 1) & 7 in bits 16..18; a null horizon is
+ *     pm_replay_push.
+ * Reported on the host before any HIP call: PM_E_SIZE: nstep outside 1..PM_NSTEP_MAX; PM_E_ARG: gamma not
+ * finite (the population call naming the member); and whatever the entry without _n rejects. */
+#define PM_NSTEP_MAX 8
+typedef struct pm_dqn_nstep {
+    uint8_t *horizon;  /* device [batch], 1..PM_NSTEP_MAX; read as ((h - 1) & 7) + 1 */
+} pm_dqn_nstep;
+size_t pm_dqn_nstep_sizeof(void);
+int pm_dqn_grads_n(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_nstep* nstep, void* stream);
+int pm_dqn_update_n(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_nstep* nstep, void* stream);
+int pm_dqn_replay_update_n(const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_nstep* nstep, const pm_dqn_replay* rp,
+                           int32_t updates, void* stream);
+int pm_dqn_nstep_pop_set(pm_dqn_pop* pop, const pm_dqn_nstep* nstep, void* stream);
+int pm_rollout_push_n(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
+                      const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net, uint64_t counter0,
+                      int32_t steps, float* heads_ws, float* obsA, float* obsB, const pm_roll_replay* rp, int64_t* stats,
+                      int32_t n, int32_t nstep, double gamma, void* stream);
+int pm_rollout_nstep_pop_set(pm_rollout_pop* pop, const int32_t* nstep, const double* gamma, void* stream);
+int pm_replay_push_n(float* trans, float* prios, void* per_work, int64_t cap, int64_t pos, float alpha, float prio,
+                     const float* s, const int32_t* act, const float* rew, const float* ns, const uint8_t* done,
+                     const uint8_t* horizon, int32_t n, void* stream);
+
 /* ---------------------------------------------------------------- QNetRNN self-play (K7) */
 
 /* scripts/train_rnn_iterative.py's hot loop (:731-798) for n arenas: both players act with their
@@ -815,7 +877,8 @@ int pm_rnn_selfplay_finish_overlap(const pm_rnn_selfplay *sp, const pm_drqn *d, 
 /* ---------------------------------------------------------------- replay + PER (K4) */
 
 /* Transition record, PM_TRANS_F floats per row (64 B): s [7] | r | s' [7] | bits(a | done << 8).
- * (memory.push((oB, aB, rB, nB, done)), scripts/train_iterative.py:243) */
+ * (memory.push((oB, aB, rB, nB, done)), scripts/train_iterative.py:243) Bits 16..18 of the last word hold an
+ * n-step row's horizon - 1 ("n-step returns" above); they are zero in one-step rows. */
 #define PM_TRANS_F 16
 
 /* PrioritizedReplay.sample (scripts/train_iterative.py:64-73): `bs` indices drawn from

@@ -96,8 +96,11 @@ __device__ __forceinline__ void store_acc_rows(float* r, int row, bool valid, in
 
 // Block-wide (kDqn threads). Returns with every store issued; the caller's barrier publishes them.
 // kOpt: o.loss selects the row loss of phase 2; without it o is not read.
-template <bool kOpt>
-__device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, const pm_dqn_opt& o, DqnSmem& sm) {
+// kN: row t's target discounts by disc(k), k = ((hz[t] - 1) & 7) + 1 its horizon (pm_dqn_nstep; a null hz is k = 1
+// for every row); without it hz is not read.
+template <bool kOpt, bool kN = false>
+__device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, const pm_dqn_opt& o, DqnSmem& sm,
+                                               const uint8_t* hz = nullptr) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int col = lane & 31, h = lane >> 5;
     const int B = d.batch, ntiles = (B + 31) >> 5, nrows = ntiles * 32;
@@ -186,7 +189,13 @@ __device__ __forceinline__ void dqn_grads_body(const pm_dqn& d, const pm_dqn_opt
             qv = sm.qa[t];
             const int na = sm.na[t];
             const float nq = na == 0 ? sm.qt[t][0] : (na == 1 ? sm.qt[t][1] : sm.qt[t][2]);
-            const float tg = d.rew[t] + ((float)d.gamma * nq) * (d.done[t] ? 0.f : 1.f);  // r + gamma * nq * (~d)
+            float disc = (float)d.gamma;
+            if (kN && hz) {  // disc(k) = disc(k - 1) * g, float32 products in that order
+                const float g = disc;
+                const int k1 = (hz[t] - 1) & 7;
+                for (int e = 0; e < k1; ++e) disc = disc * g;
+            }
+            const float tg = d.rew[t] + (disc * nq) * (d.done[t] ? 0.f : 1.f);  // r + gamma * nq * (~d)
             const float diff = qv - tg, w = d.isw ? d.isw[t] : 1.f;
             d.td[t] = fabsf(diff);
             lterm = w * (diff * diff);
@@ -489,6 +498,32 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqr_update_opt(const pm_dqn d, cons
     dqn_apply_body<true>(d, o, ak, nsq);
 }
 
+// The three with a pm_dqn_nstep's horizon buffer (pm_dqn_*_n with a non-null horizon): the _opt kernels with kN.
+__global__ __launch_bounds__(kDqn, 1) void k_dqn_grads_n(const pm_dqn d, const pm_dqn_opt o, const uint8_t* hz) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    dqn_grads_body<true, true>(d, o, sm, hz);
+}
+
+__global__ __launch_bounds__(kDqn, 1) void k_dqn_update_n(const pm_dqn d, const pm_dqn_opt o, const uint8_t* hz) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    dqn_grads_body<true, true>(d, o, sm, hz);
+    __syncthreads();
+    dqn_apply_body<true>(d, o, ak, nsq);
+}
+
+__global__ __launch_bounds__(kDqn, 1) void k_dqr_update_n(const pm_dqn d, const pm_dqn_opt o, const uint8_t* hz,
+                                                         const int64_t* gate) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    if (gate[0] < 0) return;  // block-uniform, as k_dqr_update_opt
+    dqn_grads_body<true, true>(d, o, sm, hz);
+    __syncthreads();
+    dqn_apply_body<true>(d, o, ak, nsq);
+}
+
 // One population member per workgroup: the record is block-uniform and comes in by scalar loads (pop_member, pm_pop.h).
 __global__ __launch_bounds__(kDqn, 1) void k_dqp_update(const pm_dqn_member* tab, int gated) {
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
@@ -497,6 +532,18 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqp_update(const pm_dqn_member* tab
     const pm_dqn_member m = pop_member(tab, blockIdx.x);
     if (gated && m.rp.idx[0] < 0) return;  // block-uniform: this member's update is void; the others' are not
     dqn_grads_body<true>(m.d, m.o, sm);
+    __syncthreads();
+    dqn_apply_body<true>(m.d, m.o, ak, nsq);
+}
+
+// k_dqp_update with the members' horizon buffers (pm_dqn_nstep_pop_set): hzt[p] is member p's, or null.
+__global__ __launch_bounds__(kDqn, 1) void k_dqp_update_n(const pm_dqn_member* tab, const uint8_t* const* hzt, int gated) {
+    __shared__ __attribute__((aligned(16))) DqnSmem sm;
+    __shared__ float ak[2];
+    __shared__ double nsq[kDqn / 64];
+    const pm_dqn_member m = pop_member(tab, blockIdx.x);
+    if (gated && m.rp.idx[0] < 0) return;  // block-uniform
+    dqn_grads_body<true, true>(m.d, m.o, sm, hzt[blockIdx.x]);
     __syncthreads();
     dqn_apply_body<true>(m.d, m.o, ak, nsq);
 }
@@ -559,7 +606,19 @@ int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int6
     return PM_OK;
 }
 
-int dqp_launch_update(const pm_dqn_member* tab, int n, int gated, hipStream_t st) {
+int dqn_launch_update_gated_n(const pm_dqn* d, const pm_dqn_opt* o, const uint8_t* hz, const int64_t* gate,
+                              hipStream_t st) {
+    hipLaunchKernelGGL(k_dqr_update_n, dim3(1), dim3(kDqn), 0, st, *d, opt_or_default(o), hz, gate);
+    PM_LAUNCHED("k_dqr_update_n");
+    return PM_OK;
+}
+
+int dqp_launch_update(const pm_dqn_member* tab, const uint8_t* const* hzt, int n, int gated, hipStream_t st) {
+    if (hzt) {
+        hipLaunchKernelGGL(k_dqp_update_n, dim3(n), dim3(kDqn), 0, st, tab, hzt, gated);
+        PM_LAUNCHED("k_dqp_update_n");
+        return PM_OK;
+    }
     hipLaunchKernelGGL(k_dqp_update, dim3(n), dim3(kDqn), 0, st, tab, gated);
     PM_LAUNCHED("k_dqp_update");
     return PM_OK;
@@ -608,5 +667,28 @@ extern "C" int pm_dqn_update_opt(const pm_dqn* d, const pm_dqn_opt* o, void* str
     if (int rc = check_opt(o)) return rc;
     hipLaunchKernelGGL(k_dqn_update_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
     PM_LAUNCHED("k_dqn_update_opt");
+    return PM_OK;
+}
+
+extern "C" size_t pm_dqn_nstep_sizeof(void) { return sizeof(pm_dqn_nstep); }
+
+// A null pm_dqn_nstep, or one with a null horizon, is the _opt entry as it is (the same kernel).
+extern "C" int pm_dqn_grads_n(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_nstep* ns, void* stream) {
+    if (!ns || !ns->horizon) return pm_dqn_grads_opt(d, o, stream);
+    if (int rc = check(d)) return rc;
+    if (int rc = check_opt(o)) return rc;
+    hipLaunchKernelGGL(k_dqn_grads_n, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o),
+                       (const uint8_t*)ns->horizon);
+    PM_LAUNCHED("k_dqn_grads_n");
+    return PM_OK;
+}
+
+extern "C" int pm_dqn_update_n(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_nstep* ns, void* stream) {
+    if (!ns || !ns->horizon) return pm_dqn_update_opt(d, o, stream);
+    if (int rc = check(d)) return rc;
+    if (int rc = check_opt(o)) return rc;
+    hipLaunchKernelGGL(k_dqn_update_n, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o),
+                       (const uint8_t*)ns->horizon);
+    PM_LAUNCHED("k_dqn_update_n");
     return PM_OK;
 }

@@ -17,7 +17,8 @@ namespace pm {
 // pm_dqn_replay.hip: what pm_dqn_replay_update checks behind pm_dqn's and pm_dqn_opt's own checks.
 int dqn_replay_check(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates);
 // One launch each, grid n. gated: the idx[0] < 0 gate of k_dqr_update_opt (the replay path).
-int dqp_launch_update(const pm_dqn_member* tab, int n, int gated, hipStream_t st);
-int dqp_launch_sample(const pm_dqn_member* tab, int n, int upd, hipStream_t st);
+// hzt: the members' horizon buffers (device [n], entries nullable), or null for the kernels without a horizon.
+int dqp_launch_update(const pm_dqn_member* tab, const uint8_t* const* hzt, int n, int gated, hipStream_t st);
+int dqp_launch_sample(const pm_dqn_member* tab, uint8_t* const* hzt, int n, int upd, hipStream_t st);
 int dqp_launch_scatter(const pm_dqn_member* tab, int n, hipStream_t st);
 }  // namespace pm

@@ -17,6 +17,10 @@ struct pm_dqn_pop {
     pm_dqn_member* tab;  // device, [n]
     int32_t n;
     int32_t has_replay;
+    std::vector<pm_dqn_member> host;  // the bound table, for pm_dqn_nstep_pop_set's aliasing check
+    std::vector<uint8_t*> hz;         // the members' horizon buffers (pm_dqn_nstep_pop_set): empty, or n entries
+    uint8_t** hz_dev;                 // device copy of hz once one was attached, else null
+    int32_t use_n;                    // a member has a horizon buffer: the launches are the _n kernels
 };
 
 namespace {
@@ -25,8 +29,10 @@ using pm::PopRange;
 constexpr auto add = pm::pop_add;
 
 // Every buffer a launch may write for member p, with its size in bytes.
-void writable(std::vector<PopRange>& v, int p, const pm_dqn& d, const pm_dqn_opt& o, const pm_dqn_replay* rp) {
+void writable(std::vector<PopRange>& v, int p, const pm_dqn& d, const pm_dqn_opt& o, const pm_dqn_replay* rp,
+              const uint8_t* hz) {
     const size_t B = (size_t)d.batch;
+    add(v, p, "horizon", hz, B);  // the replay gather writes it
     add(v, p, "params", d.params, sizeof(float) * PM_QNET_NP);
     add(v, p, "target", d.target, sizeof(float) * PM_QNET_NP);
     add(v, p, "adam_m", d.adam_m, sizeof(float) * PM_DQN_NPARAM);
@@ -50,7 +56,7 @@ void writable(std::vector<PopRange>& v, int p, const pm_dqn& d, const pm_dqn_opt
 
 // Everything pm_dqn_pop_create and _rebind reject, and the table they upload. No HIP call.
 int build_table(const char* who, const pm_dqn* d, const pm_dqn_opt* opt, const pm_dqn_replay* rp, int32_t n,
-                std::vector<pm_dqn_member>& tab) {
+                std::vector<pm_dqn_member>& tab, const std::vector<uint8_t*>& hz) {
     PM_REQUIRE(n >= 1 && n <= PM_DQN_POP_MAX, PM_E_SIZE, "%s: n=%d (1..%d)", who, n, PM_DQN_POP_MAX);
     PM_REQUIRE(d, PM_E_ARG, "%s: null descriptor array", who);
     tab.assign((size_t)n, pm_dqn_member{});
@@ -68,7 +74,8 @@ int build_table(const char* who, const pm_dqn* d, const pm_dqn_opt* opt, const p
     }
     std::vector<PopRange> v;
     v.reserve((size_t)n * 18);
-    for (int p = 0; p < n; ++p) writable(v, p, tab[p].d, tab[p].o, rp ? &tab[p].rp : nullptr);
+    for (int p = 0; p < n; ++p)
+        writable(v, p, tab[p].d, tab[p].o, rp ? &tab[p].rp : nullptr, hz.empty() ? nullptr : hz[(size_t)p]);
     return pm::pop_check_overlap(who, v);
 }
 
@@ -80,10 +87,10 @@ extern "C" int pm_dqn_pop_create(const pm_dqn* d, const pm_dqn_opt* opt, const p
     PM_REQUIRE(out, PM_E_ARG, "%s: null out", who);
     *out = nullptr;
     std::vector<pm_dqn_member> tab;
-    if (int rc = build_table(who, d, opt, rp, n, tab)) return rc;
+    if (int rc = build_table(who, d, opt, rp, n, tab, {})) return rc;
     pm_dqn_member* dev;
     if (int rc = pm::pop_table_create(who, tab.data(), sizeof(pm_dqn_member) * (size_t)n, (void**)&dev)) return rc;
-    *out = new pm_dqn_pop{dev, n, rp ? 1 : 0};
+    *out = new pm_dqn_pop{dev, n, rp ? 1 : 0, std::move(tab), {}, nullptr, 0};
     return PM_OK;
 }
 
@@ -92,16 +99,45 @@ extern "C" int pm_dqn_pop_rebind(pm_dqn_pop* pop, const pm_dqn* d, const pm_dqn_
     const char* who = "pm_dqn_pop_rebind";
     PM_REQUIRE(pop, PM_E_ARG, "%s: null handle", who);
     std::vector<pm_dqn_member> tab;
-    if (int rc = build_table(who, d, opt, rp, pop->n, tab)) return rc;
+    if (int rc = build_table(who, d, opt, rp, pop->n, tab, pop->hz)) return rc;
     if (int rc = pm::pop_table_rebind(who, pop->tab, tab.data(), sizeof(pm_dqn_member) * (size_t)pop->n, pm_stream(stream)))
         return rc;
     pop->has_replay = rp ? 1 : 0;
+    pop->host = std::move(tab);
+    return PM_OK;
+}
+
+extern "C" int pm_dqn_nstep_pop_set(pm_dqn_pop* pop, const pm_dqn_nstep* ns, void* stream) {
+    const char* who = "pm_dqn_nstep_pop_set";
+    PM_REQUIRE(pop, PM_E_ARG, "%s: null handle", who);
+    const size_t n = (size_t)pop->n;
+    std::vector<uint8_t*> hz(n, nullptr);
+    int32_t use_n = 0;
+    for (size_t p = 0; ns && p < n; ++p) {
+        hz[p] = ns[p].horizon;
+        if (hz[p]) use_n = 1;
+    }
+    std::vector<PopRange> v;
+    v.reserve(n * 19);
+    for (size_t p = 0; p < n; ++p)
+        writable(v, (int)p, pop->host[p].d, pop->host[p].o, pop->has_replay ? &pop->host[p].rp : nullptr, hz[p]);
+    if (int rc = pm::pop_check_overlap(who, v)) return rc;
+    if (pop->hz_dev) {  // launches on the stream read the old pointers: they finish first
+        if (int rc = pm::pop_table_rebind(who, pop->hz_dev, hz.data(), sizeof(uint8_t*) * n, pm_stream(stream))) return rc;
+    } else if (use_n) {
+        if (int rc = pm::pop_table_create(who, hz.data(), sizeof(uint8_t*) * n, (void**)&pop->hz_dev)) {
+            pop->hz_dev = nullptr;
+            return rc;
+        }
+    }
+    pop->hz = use_n ? std::move(hz) : std::vector<uint8_t*>{};
+    pop->use_n = use_n;
     return PM_OK;
 }
 
 extern "C" int pm_dqn_pop_update(const pm_dqn_pop* pop, void* stream) {
     PM_REQUIRE(pop, PM_E_ARG, "pm_dqn_pop_update: null handle");
-    return pm::dqp_launch_update(pop->tab, pop->n, 0, pm_stream(stream));
+    return pm::dqp_launch_update(pop->tab, pop->use_n ? pop->hz_dev : nullptr, pop->n, 0, pm_stream(stream));
 }
 
 extern "C" int pm_dqn_pop_replay_update(const pm_dqn_pop* pop, int32_t updates, void* stream) {
@@ -109,9 +145,10 @@ extern "C" int pm_dqn_pop_replay_update(const pm_dqn_pop* pop, int32_t updates, 
     PM_REQUIRE(pop->has_replay, PM_E_ARG, "pm_dqn_pop_replay_update: the population was created without replay descriptors");
     PM_REQUIRE(updates > 0, PM_E_SIZE, "pm_dqn_pop_replay_update: updates=%d", updates);
     hipStream_t st = pm_stream(stream);
+    uint8_t* const* hzt = pop->use_n ? pop->hz_dev : nullptr;
     for (int k = 0; k < updates; ++k) {
-        if (int rc = pm::dqp_launch_sample(pop->tab, pop->n, k, st)) return rc;
-        if (int rc = pm::dqp_launch_update(pop->tab, pop->n, 1, st)) return rc;
+        if (int rc = pm::dqp_launch_sample(pop->tab, hzt, pop->n, k, st)) return rc;
+        if (int rc = pm::dqp_launch_update(pop->tab, hzt, pop->n, 1, st)) return rc;
         if (int rc = pm::dqp_launch_scatter(pop->tab, pop->n, st)) return rc;
     }
     return PM_OK;
@@ -126,7 +163,9 @@ extern "C" int pm_dqn_pop_info(const pm_dqn_pop* pop, int32_t* n, int32_t* has_r
 
 extern "C" int pm_dqn_pop_destroy(pm_dqn_pop* pop) {
     PM_REQUIRE(pop, PM_E_ARG, "pm_dqn_pop_destroy: null handle");
-    const int rc = pm::pop_table_free("pm_dqn_pop_destroy", pop->tab);
+    int rc = pm::pop_table_free("pm_dqn_pop_destroy", pop->tab);
+    if (pop->hz_dev)
+        if (const int rc2 = pm::pop_table_free("pm_dqn_pop_destroy", pop->hz_dev)) rc = rc2;
     delete pop;  // even when hipFree failed
     return rc;
 }

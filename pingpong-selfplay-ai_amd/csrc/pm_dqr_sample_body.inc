@@ -3,7 +3,8 @@
 // It is shared as text, not as a __device__ function, because k_dqr_sample must keep its device text: routed
 // through a function the compiler schedules seven instructions of the weights' maximum in another order
 // (tools/kernel_text.py: DIFFER), whichever way the descriptors are handed over. k_dqr_scatter's body, which
-// does keep its text behind a function, is one (dqr_scatter_body).
+// does keep its text behind a function, is one (dqr_scatter_body). PM_DQR_HORIZON(j, bits) is the including kernel's
+// own: nothing in k_dqr_sample / k_dqp_sample, the store of row j's horizon byte in their _n forms.
     const int t = threadIdx.x, wv = t >> 6, B = d.batch;
     const int64_t frame = d.stats->steps + 1;  // frame_idx += 1 before sampling (:136)
     const double b = rp.beta_start + (double)frame * (1.0 - rp.beta_start) / (double)rp.beta_frames;  // :137
@@ -62,5 +63,6 @@
             const int bits = __float_as_int(x.w);
             act[j] = bits & 0xff;
             done[j] = (uint8_t)((bits >> 8) & 1);
+            PM_DQR_HORIZON(j, bits);
         }
     }

@@ -40,6 +40,8 @@ int dqn_launch_update_gated(const pm_dqn* d, const int64_t* gate, hipStream_t st
 // The same two with a pm_dqn_opt (null = the defaults): its check, and k_dqr_update_opt's launch.
 int dqn_check_opt(const pm_dqn_opt* o);
 int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int64_t* gate, hipStream_t st);
+int dqn_launch_update_gated_n(const pm_dqn* d, const pm_dqn_opt* o, const uint8_t* hz, const int64_t* gate,
+                              hipStream_t st);
 }  // namespace pm
 
 // Launch timing (pm_timer_arm / pm_timer_read, pm_api.cpp): an armed kernel's next launch goes

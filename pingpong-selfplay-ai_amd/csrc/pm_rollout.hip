@@ -33,6 +33,8 @@
 // Bit-identical to `steps` repetitions of pm_qnet_fold(paramsB, FRESH, seed_net, c) ->
 // pm_qnet_act({wA}, NULL, w_B, obsA, obsB, epsilon, seed_env, c) -> pm_env_step(autoreset, seed_env,
 // c) with c = counter0 + s (tests/test_gpu_rollout.py).
+#include <cmath>
+
 #include "pm_host.h"
 #include "pm_mfma.h"
 #include "pm_per.h"
@@ -57,7 +59,19 @@ __global__ __launch_bounds__(kRollBlock) __attribute__((amdgpu_waves_per_eu(3, 3
     const pm_env_params p, const pm_env_state s, const float* __restrict__ wA, const float* __restrict__ wB,
     const float* __restrict__ ws, double eps, uint64_t seed_env, uint64_t counter0, int steps,
     float* __restrict__ obsA, float* __restrict__ obsB, long long* __restrict__ stats, int n, const RollPush rp) {
-    rollout_push_body(p, s, wA, wB, ws, eps, seed_env, counter0, steps, obsA, obsB, stats, n, rp, blockIdx.x);
+    rollout_push_body<false>(p, s, wA, wB, ws, eps, seed_env, counter0, steps, obsA, obsB, stats, n, rp, RollN{},
+                             blockIdx.x);
+}
+
+// pm_rollout_push_n with nstep > 1: the same launch with wave 3's n-step window (nstep_push). The window's 9 KB
+// of LDS leave two blocks per CU, so the kernel takes the compiler's own register budget instead of the cap.
+__global__ __launch_bounds__(kRollBlock) void k_rollout_push_n(
+    const pm_env_params p, const pm_env_state s, const float* __restrict__ wA, const float* __restrict__ wB,
+    const float* __restrict__ ws, double eps, uint64_t seed_env, uint64_t counter0, int steps,
+    float* __restrict__ obsA, float* __restrict__ obsB, long long* __restrict__ stats, int n, const RollPush rp,
+    const RollN rn) {
+    rollout_push_body<true>(p, s, wA, wB, ws, eps, seed_env, counter0, steps, obsA, obsB, stats, n, rp, rn,
+                            blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -380,7 +394,7 @@ __global__ __launch_bounds__(kR16Block) void k_rollout16(const pm_env_params p, 
 static int rollout_launch(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
                           const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net, uint64_t counter0,
                           int32_t steps, float* heads_ws, float* obsA, float* obsB, const RollPush* rp, void* per_work,
-                          int64_t* stats, int32_t n, void* stream) {
+                          int64_t* stats, int32_t n, void* stream, const RollN* rn = nullptr) {
     const char* name = rp ? "pm_rollout_push" : "pm_rollout";
     PM_REQUIRE(n >= 0 && steps >= 0, PM_E_SIZE, "%s: n=%d steps=%d", name, n, steps);
     if (n == 0 || steps == 0) return PM_OK;
@@ -393,6 +407,14 @@ static int rollout_launch(const pm_env_params* p, const pm_env_state* s, const f
     hipStream_t st = pm_stream(stream);
     hipLaunchKernelGGL(k_rollout_heads, dim3(steps), dim3(kHeadsBlock), 0, st, paramsB, seed_net, counter0, heads_ws);
     PM_LAUNCHED("k_rollout_heads");
+    if (rp && rn) {
+        pm_launch(PM_TIMER_ROLLOUT, k_rollout_push_n, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
+                  (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
+                  reinterpret_cast<long long*>(stats), n, *rp, *rn);
+        PM_LAUNCHED("k_rollout_push_n");
+        if (per_work) return per_launch_nodes(per_work, rp->cap, st);
+        return PM_OK;
+    }
     if (rp) {
         pm_launch(PM_TIMER_ROLLOUT, k_rollout_push, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
                   (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
@@ -422,10 +444,11 @@ extern "C" int pm_rollout(const pm_env_params* p, const pm_env_state* s, const f
                           nullptr, nullptr, stats, n, stream);
 }
 
-extern "C" int pm_rollout_push(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
-                               const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net,
-                               uint64_t counter0, int32_t steps, float* heads_ws, float* obsA, float* obsB,
-                               const pm_roll_replay* rp, int64_t* stats, int32_t n, void* stream) {
+// pm_rollout_push (rn null) and pm_rollout_push_n with nstep > 1.
+static int rollout_push(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
+                        const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net, uint64_t counter0,
+                        int32_t steps, float* heads_ws, float* obsA, float* obsB, const pm_roll_replay* rp,
+                        int64_t* stats, int32_t n, void* stream, const RollN* rn) {
     PM_REQUIRE(rp && rp->trans && rp->prios && rp->ep_reward, PM_E_ARG, "pm_rollout_push: null replay buffer");
     PM_REQUIRE(rp->cap > 0 && rp->pos >= 0 && rp->pos < rp->cap, PM_E_SIZE, "pm_rollout_push: pos=%lld cap=%lld",
                (long long)rp->pos, (long long)rp->cap);
@@ -437,5 +460,26 @@ extern "C" int pm_rollout_push(const pm_env_params* p, const pm_env_state* s, co
     const RollPush d{rp->trans, rp->prios, rp->per_work ? per_tree(rp->per_work, rp->cap).leaf : nullptr,
                      rp->ep_reward, rp->pos, rp->cap, rp->prio, rp->alpha};
     return rollout_launch(p, s, wA, wB, paramsB, epsilon, seed_env, seed_net, counter0, steps, heads_ws, obsA, obsB,
-                          &d, rp->per_work, stats, n, stream);
+                          &d, rp->per_work, stats, n, stream, rn);
+}
+
+extern "C" int pm_rollout_push(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
+                               const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net,
+                               uint64_t counter0, int32_t steps, float* heads_ws, float* obsA, float* obsB,
+                               const pm_roll_replay* rp, int64_t* stats, int32_t n, void* stream) {
+    return rollout_push(p, s, wA, wB, paramsB, epsilon, seed_env, seed_net, counter0, steps, heads_ws, obsA, obsB, rp,
+                        stats, n, stream, nullptr);
+}
+
+extern "C" int pm_rollout_push_n(const pm_env_params* p, const pm_env_state* s, const float* wA, const float* wB,
+                                 const float* paramsB, float epsilon, uint64_t seed_env, uint64_t seed_net,
+                                 uint64_t counter0, int32_t steps, float* heads_ws, float* obsA, float* obsB,
+                                 const pm_roll_replay* rp, int64_t* stats, int32_t n, int32_t nstep, double gamma,
+                                 void* stream) {
+    PM_REQUIRE(nstep >= 1 && nstep <= PM_NSTEP_MAX, PM_E_SIZE, "pm_rollout_push_n: nstep=%d (1..%d)", nstep,
+               PM_NSTEP_MAX);
+    PM_REQUIRE(std::isfinite(gamma), PM_E_ARG, "pm_rollout_push_n: gamma is not finite");
+    const RollN rn{nstep, (float)gamma};
+    return rollout_push(p, s, wA, wB, paramsB, epsilon, seed_env, seed_net, counter0, steps, heads_ws, obsA, obsB, rp,
+                        stats, n, stream, nstep > 1 ? &rn : nullptr);  // nstep 1: the one-step launch as it is
 }

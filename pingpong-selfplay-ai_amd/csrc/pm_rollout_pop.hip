@@ -40,6 +40,8 @@ struct pm_rollout_pop {
     int32_t n, m, steps_max;
     int32_t any_prio;     // a member has prio_dev
     int64_t node_blocks;  // the most 64-node blocks any member's tree has (0: no member has per_work)
+    void* rn;             // device RollN [n] once pm_rollout_nstep_pop_set has given a horizon above 1, else null
+    int32_t use_n;        // a member's nstep is above 1: the push is k_rpp_push_n
 };
 
 namespace {
@@ -127,8 +129,35 @@ __global__ __launch_bounds__(kRollBlock) __attribute__((amdgpu_waves_per_eu(3, 3
                       mb.rp.cap,
                       prio,
                       mb.rp.alpha};
-    rollout_push_body(p, sl, mb.wA, mb.wB, mb.heads_ws, (double)mb.epsilon, mb.seed_env, counter0, steps,
-                      obsA + off * 7, obsB + off * 7, reinterpret_cast<long long*>(mb.stats), m, rp, (int)tile);
+    rollout_push_body<false>(p, sl, mb.wA, mb.wB, mb.heads_ws, (double)mb.epsilon, mb.seed_env, counter0, steps,
+                             obsA + off * 7, obsB + off * 7, reinterpret_cast<long long*>(mb.stats), m, rp, RollN{},
+                             (int)tile);
+}
+
+// k_rpp_push with the n-step window (k_rollout_push_n's body), member p's horizon and discount in rnt[p]; a member
+// with nstep 1 writes the one-step rows. Like the solo kernel it takes the compiler's own register budget.
+__global__ __launch_bounds__(kRollBlock) void k_rpp_push_n(
+    const pm_env_params p, const pm_env_state s, const pm_roll_member* __restrict__ tab,
+    const RollN* __restrict__ rnt, int m, int tiles, uint64_t counter0, int steps, int64_t advance,
+    float* __restrict__ obsA, float* __restrict__ obsB) {
+    const unsigned mem = blockIdx.x / (unsigned)tiles, tile = blockIdx.x - mem * (unsigned)tiles;
+    const pm_roll_member mb = pop_member(tab, mem);
+    const RollN rn = rnt[mem];
+    const size_t off = (size_t)mem * (size_t)m;  // the member's first arena
+    const pm_env_state sl{s.x + off,   s.y + off,   s.vx + off,     s.vy + off,     s.spin + off,    s.top + off,
+                          s.bot + off, s.scoreA + off, s.scoreB + off, s.bounces + off, nullptr};
+    const float prio = mb.prio_dev ? mb.prio_dev[0] : mb.rp.prio;
+    const RollPush rp{mb.rp.trans,
+                      mb.rp.prios,
+                      mb.rp.per_work ? per_tree(mb.rp.per_work, mb.rp.cap).leaf : nullptr,
+                      mb.rp.ep_reward,
+                      rpp_pos(mb, advance),
+                      mb.rp.cap,
+                      prio,
+                      mb.rp.alpha};
+    rollout_push_body<true>(p, sl, mb.wA, mb.wB, mb.heads_ws, (double)mb.epsilon, mb.seed_env, counter0, steps,
+                            obsA + off * 7, obsB + off * 7, reinterpret_cast<long long*>(mb.stats), m, rp, rn,
+                            (int)tile);
 }
 
 // k_per_nodes (pm_replay.hip) per member, on the member's tree. No pending push range: the leaves are written.
@@ -215,7 +244,7 @@ extern "C" int pm_rollout_pop_create(const pm_env_params* p, const pm_env_state*
     if (int rc = check_table(who, members, n, m, steps_max, &any_prio, &node_blocks)) return rc;
     pm_roll_member* dev;
     if (int rc = pop_table_create(who, members, sizeof(pm_roll_member) * (size_t)n, (void**)&dev)) return rc;
-    *out = new pm_rollout_pop{dev, *p, *s, n, m, steps_max, any_prio, node_blocks};
+    *out = new pm_rollout_pop{dev, *p, *s, n, m, steps_max, any_prio, node_blocks, nullptr, 0};
     return PM_OK;
 }
 
@@ -249,14 +278,47 @@ extern "C" int pm_rollout_pop_push(const pm_rollout_pop* pop, uint64_t counter0,
     }
     hipLaunchKernelGGL(k_rpp_heads, dim3(steps, n), dim3(kHeadsBlock), 0, st, (const pm_roll_member*)pop->tab, counter0);
     PM_LAUNCHED("k_rpp_heads");
-    pm_launch(PM_TIMER_ROLLOUT, k_rpp_push, dim3((unsigned)n * (unsigned)tiles), dim3(kRollBlock), st, pop->p, pop->s,
-              (const pm_roll_member*)pop->tab, m, tiles, counter0, (int)steps, advance, obsA, obsB);
-    PM_LAUNCHED("k_rpp_push");
+    if (pop->use_n) {
+        pm_launch(PM_TIMER_ROLLOUT, k_rpp_push_n, dim3((unsigned)n * (unsigned)tiles), dim3(kRollBlock), st, pop->p,
+                  pop->s, (const pm_roll_member*)pop->tab, (const RollN*)pop->rn, m, tiles, counter0, (int)steps,
+                  advance, obsA, obsB);
+        PM_LAUNCHED("k_rpp_push_n");
+    } else {
+        pm_launch(PM_TIMER_ROLLOUT, k_rpp_push, dim3((unsigned)n * (unsigned)tiles), dim3(kRollBlock), st, pop->p,
+                  pop->s, (const pm_roll_member*)pop->tab, m, tiles, counter0, (int)steps, advance, obsA, obsB);
+        PM_LAUNCHED("k_rpp_push");
+    }
     if (pop->node_blocks) {
         hipLaunchKernelGGL(k_rpp_nodes, dim3((unsigned)pop->node_blocks, n), dim3(256), 0, st,
                            (const pm_roll_member*)pop->tab);
         PM_LAUNCHED("k_rpp_nodes");
     }
+    return PM_OK;
+}
+
+extern "C" int pm_rollout_nstep_pop_set(pm_rollout_pop* pop, const int32_t* nstep, const double* gamma, void* stream) {
+    const char* who = "pm_rollout_nstep_pop_set";
+    PM_REQUIRE(pop, PM_E_ARG, "%s: null handle", who);
+    PM_REQUIRE(!nstep == !gamma, PM_E_ARG, "%s: nstep and gamma are given together, or both null", who);
+    std::vector<RollN> rn((size_t)pop->n, RollN{1, 0.f});
+    int32_t use_n = 0;
+    for (int p = 0; nstep && p < pop->n; ++p) {
+        PM_REQUIRE(nstep[p] >= 1 && nstep[p] <= PM_NSTEP_MAX, PM_E_SIZE, "%s: member %d: nstep=%d (1..%d)", who, p,
+                   nstep[p], PM_NSTEP_MAX);
+        PM_REQUIRE(std::isfinite(gamma[p]), PM_E_ARG, "%s: member %d: gamma is not finite", who, p);
+        rn[(size_t)p] = RollN{nstep[p], (float)gamma[p]};
+        if (nstep[p] > 1) use_n = 1;
+    }
+    const size_t bytes = sizeof(RollN) * (size_t)pop->n;
+    if (pop->rn) {  // launches on the stream read the old horizons: they finish first
+        if (int rc = pop_table_rebind(who, pop->rn, rn.data(), bytes, pm_stream(stream))) return rc;
+    } else if (use_n) {
+        if (int rc = pop_table_create(who, rn.data(), bytes, &pop->rn)) {
+            pop->rn = nullptr;
+            return rc;
+        }
+    }
+    pop->use_n = use_n;
     return PM_OK;
 }
 
@@ -270,7 +332,9 @@ extern "C" int pm_rollout_pop_info(const pm_rollout_pop* pop, int32_t* n, int32_
 
 extern "C" int pm_rollout_pop_destroy(pm_rollout_pop* pop) {
     PM_REQUIRE(pop, PM_E_ARG, "pm_rollout_pop_destroy: null handle");
-    const int rc = pop_table_free("pm_rollout_pop_destroy", pop->tab);
+    int rc = pop_table_free("pm_rollout_pop_destroy", pop->tab);
+    if (pop->rn)
+        if (const int rc2 = pop_table_free("pm_rollout_pop_destroy", pop->rn)) rc = rc2;
     delete pop;  // even when hipFree failed
     return rc;
 }

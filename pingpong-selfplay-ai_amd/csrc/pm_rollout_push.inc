@@ -130,14 +130,87 @@ __device__ __forceinline__ void roll_draws(const pm_env_params& p, RollShared& s
     }
 }
 
+// The n-step window (pm_rollout_push_n): the launch's horizon N = nstep (1..PM_NSTEP_MAX) and g = (float)gamma.
+struct RollN {
+    int nstep;
+    float g;
+};
+
+// Wave 3's pending transitions, per arena column: the one opened at step t sits in entry t & 7 until it is
+// written (at most N <= 8 are pending, opened at consecutive steps, so no entry is reused while it is live).
+// Lanes 0-31 own s | R, the half of the row they store; lanes 32-63 own the action, which goes into theirs.
+// A pending transition's age is the step minus its opening step, so neither k nor f = g^age is stored.
+struct RollWindow {
+    __attribute__((aligned(16))) float sr[PM_NSTEP_MAX][32][8];  // s[7], R
+    int act[PM_NSTEP_MAX][32];
+};
+
+// One step of the n-step window of arena i, for wave 3's lanes with a valid arena (lanes < 32 and lanes >= 32 hold
+// the same arena and make the same decisions). Step st's transition (s = oB, aB) is opened; every pending one,
+// age j = st - its opening step, takes the step's reward as R = R + g^j * rB (g^j the float32 product chain
+// disc(j), g^0 = 1); then a pending transition is written with its horizon k = j + 1 if the episode ended
+// (done = 1, all of them), if it has reached k = N, or at the launch's last step (done = 0). s' is the
+// observation after the tick, before the serve. The one opened at step t goes to slot (pos + t * n + i) mod cap.
+__device__ __forceinline__ void nstep_push(const RollPush& rp, const RollN& rn, int st, bool last, int n, int i,
+                                           int lane, int col, const float (&oB)[7], int aB, float rB, int d,
+                                           const Arena& a, int& first, float leafv) {
+    __shared__ RollWindow win;
+    const bool hi = lane >= 32;
+    const int N = rn.nstep;
+    if (!hi) {
+        float4* e = reinterpret_cast<float4*>(win.sr[st & 7][col]);
+        e[0] = make_float4(oB[0], oB[1], oB[2], oB[3]);
+        e[1] = make_float4(oB[4], oB[5], oB[6], 0.f);
+    } else {
+        win.act[st & 7][col] = aB;
+    }
+    float nA[7], nB[7];
+    observe(a, nA, nB);
+    float f = 1.0f;
+#pragma unroll
+    for (int j = 0; j < PM_NSTEP_MAX; ++j) {
+        const int t = st - j;
+        if (j < N && t >= first) {
+            const int w = t & 7;
+            const bool write = d || last || j == N - 1;
+            float4 lo0 = make_float4(0.f, 0.f, 0.f, 0.f), lo1 = lo0;
+            int act = 0;
+            if (!hi) {
+                const float4* e = reinterpret_cast<const float4*>(win.sr[w][col]);
+                lo0 = e[0];
+                lo1 = e[1];
+                lo1.w = lo1.w + f * rB;
+                if (!write) win.sr[w][col][7] = lo1.w;
+            } else if (write) {
+                act = win.act[w][col];
+            }
+            if (write) {
+                int64_t slot = rp.pos + (int64_t)t * n + i;
+                if (slot >= rp.cap) slot -= rp.cap;
+                float4* row = reinterpret_cast<float4*>(rp.trans + slot * PM_TRANS_F) + (lane >> 5) * 2;
+                st_f4<false>(row, hi ? make_float4(nB[0], nB[1], nB[2], nB[3]) : lo0);
+                st_f4<false>(row + 1, hi ? make_float4(nB[4], nB[5], nB[6], __int_as_float(act | (d << 8) | (j << 16)))
+                                         : lo1);
+                if (!hi) rp.prios[slot] = rp.prio;
+                else if (rp.leaf) rp.leaf[slot] = leafv;
+            }
+        }
+        f = f * rn.g;
+    }
+    if (d || last) first = st + 1;
+    else if (st - first + 1 == N) first += 1;
+}
+
 // The bodies of both rollout kernels stay forceinline functions behind thin kernels: written straight
 // into the kernel (parameters by value, not by reference) the same source compiles to different code.
+// kN: the n-step variant (rn is read only there). The <false> instantiation is the one-step launch as it was.
+template <bool kN>
 __device__ __forceinline__ void rollout_push_body(const pm_env_params& p, const pm_env_state& s,
                                                   const float* __restrict__ wA, const float* __restrict__ wB,
                                                   const float* __restrict__ ws, double eps, uint64_t seed_env,
                                                   uint64_t counter0, int steps, float* __restrict__ obsA,
                                                   float* __restrict__ obsB, long long* __restrict__ stats, int n,
-                                                  const RollPush& rp, int tile) {
+                                                  const RollPush& rp, const RollN& rn, int tile) {
     __shared__ __attribute__((aligned(16))) RollShared sm;
     const int lane = threadIdx.x & 63, col = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: SGPRs, not VGPRs
@@ -150,6 +223,7 @@ __device__ __forceinline__ void rollout_push_body(const pm_env_params& p, const 
     Arena a{};
     int fin = 0, winB = 0, ptA = 0, ptB = 0, winE = 0, rsum = 0;  // per arena: |count| <= steps < 2^31
     float er = 0.f, leafv = 0.f;
+    [[maybe_unused]] int first = 0;  // kN: the opening step of the arena's oldest pending transition
     if (wv == 3) {
         a = load_arena(s, valid ? i : n - 1);
         float oA[7], oB[7];
@@ -208,7 +282,9 @@ __device__ __forceinline__ void rollout_push_body(const pm_env_params& p, const 
                 winE += er > 0.f ? 1 : 0;
                 rsum += (int)er;
             }
-            if (valid) {  // memory.push((oB, aB, rB, nB, done)): lanes < 32 s, lanes >= 32 s'
+            if constexpr (kN) {
+                if (valid) nstep_push(rp, rn, st, st + 1 == steps, n, i, lane, col, oB, aB, rB, d, a, first, leafv);
+            } else if (valid) {  // memory.push((oB, aB, rB, nB, done)): lanes < 32 s, lanes >= 32 s'
                 float nA[7], nB[7];
                 observe(a, nA, nB);  // the terminal observation, before the serve
                 int64_t slot = rp.pos + (int64_t)st * n + i;

@@ -37,6 +37,7 @@ PM_MAX_BATCH = 256
 PM_FOLD_EVAL, PM_FOLD_TRAIN, PM_FOLD_TRAIN_FRESH = 0, 1, 2
 PM_DQN_LOSS_SQUARED, PM_DQN_LOSS_HUBER = 0, 1
 PM_DQN_POP_MAX = 1024
+PM_NSTEP_MAX = 8
 PM_ACT_ALL, PM_ACT_B, PM_ACT_A = 0, 1, 2
 PM_UPD_FIRST, PM_UPD_LAST = 1, 2
 PM_COMM_ID_BYTES = 128
@@ -133,6 +134,10 @@ class DqnOpt(ctypes.Structure):
     _fields_ = [("loss", c_i32), ("_pad", c_i32), ("huber_beta", c_double), ("max_norm", c_double), ("norm", c_void_p)]
 
 
+class DqnNstep(ctypes.Structure):
+    _fields_ = [("horizon", c_void_p)]
+
+
 class RnnCtrl(ctypes.Structure):
     _fields_ = [("step", c_u64), ("episodes", c_i64), ("seq_count", c_i64), ("seq_size", c_i64), ("epsilon", c_double),
                 ("win_A", c_i64), ("ep_A", c_i64), ("win_P", c_i64), ("ep_P", c_i64), ("reward_B", c_double),
@@ -227,6 +232,17 @@ _SIGS = {
     "pm_rollout_pop_destroy": (c_i32, [c_void_p]),
     "pm_replay_push": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
+    "pm_dqn_nstep_sizeof": (ctypes.c_size_t, []),
+    "pm_dqn_grads_n": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_update_n": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_dqn_replay_update_n": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
+    "pm_dqn_nstep_pop_set": (c_i32, [c_void_p, c_void_p, c_void_p]),
+    "pm_rollout_push_n": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_u64, c_u64, c_u64,
+                                  c_i32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_double,
+                                  c_void_p]),
+    "pm_rollout_nstep_pop_set": (c_i32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pm_replay_push_n": (c_i32, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_float, c_float, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_i32, c_void_p]),
     "pm_rnn_selfplay_init": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_act": (c_i32, [c_void_p, c_void_p]),
     "pm_rnn_selfplay_env": (c_i32, [c_void_p, c_void_p, c_void_p]),
@@ -312,6 +328,9 @@ def load():
     if L.pm_roll_member_sizeof() != ctypes.sizeof(RollMember):  # likewise
         raise PongmiError(f"struct layout mismatch for RollMember: C {L.pm_roll_member_sizeof()} "
                           f"vs ctypes {ctypes.sizeof(RollMember)}")
+    if L.pm_dqn_nstep_sizeof() != ctypes.sizeof(DqnNstep):  # likewise
+        raise PongmiError(f"struct layout mismatch for DqnNstep: C {L.pm_dqn_nstep_sizeof()} "
+                          f"vs ctypes {ctypes.sizeof(DqnNstep)}")
     _lib = L
     return L
 

@@ -34,6 +34,33 @@ ALL_SHAPES = [s for _, s in PARAM_LAYOUT[:12]]   # modelB.parameters() order
 HEAD_SHAPES = [s for _, s in PARAM_LAYOUT[4:12]]  # list(fc_V.parameters()) + list(fc_A.parameters()) (:101-104)
 
 
+def check_nstep(who, v):
+    """nstep as a learner keeps it (1..PM_NSTEP_MAX), or ValueError in `who`'s name."""
+    if int(v) != v or not 1 <= int(v) <= _lib.PM_NSTEP_MAX:
+        raise ValueError(f"{who}: nstep {v!r} (1..{_lib.PM_NSTEP_MAX})")
+    return int(v)
+
+
+def load_horizon(who, buf, nstep, rows, horizon):
+    """Fill rows [0, rows) of a learner's horizon buffer: the given horizons, or nstep for every row. A learner
+    built with nstep=1 has no buffer and takes no horizons."""
+    if buf is None:
+        if horizon is not None:
+            raise _lib.PongmiError(f"{who}: horizons given to a learner built with nstep=1 (it would discount every "
+                                   "row by gamma)")
+        return
+    if horizon is None:
+        buf[:rows].fill_(nstep)
+    else:
+        buf[:rows].copy_(torch.as_tensor(horizon).reshape(rows))
+
+
+def check_replay_horizon(who, replay, nstep):
+    if replay.max_horizon > 1 and nstep == 1:
+        raise _lib.PongmiError(f"{who}: the replay holds rows of horizon up to {replay.max_horizon} and the learner was "
+                               "built with nstep=1 (it would discount every row by gamma); build it with nstep > 1")
+
+
 def check_option(who, name, v):
     """loss, huber_beta or max_norm as a learner keeps it, or ValueError in `who`'s name."""
     if name == "loss":
@@ -55,20 +82,24 @@ BUFFERS = ("params", "target", "adam_m", "adam_v", "grad", "stats_buf", "s", "ns
 class DQNLearner:
     def __init__(self, modelB, target=None, *, batch=256, gamma=0.99, lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8,
                  target_update_interval=1000, train_features=False, fresh_noise=True, seed=0, device="cuda",
-                 loss="mse", huber_beta=1.0, max_norm=None):
+                 loss="mse", huber_beta=1.0, max_norm=None, nstep=1):
         """modelB / target: a QNet module, its state_dict, or a packed [PM_QNET_NP] tensor; target None = a
         copy of modelB (copy.deepcopy(modelB), :100). batch: the most rows an update takes (1..256).
         loss: "mse" (the reference's importance-weighted squared loss) or "huber"
         ((isw * F.smooth_l1_loss(q, t, reduction='none', beta=huber_beta)).mean()). max_norm: None, or
         clip_grad_norm_(the trained parameters, max_norm) between the gradient and Adam; stats() then
         also reports the total norm before the clip. With both at their defaults every call goes to the
-        plain entry points."""
+        plain entry points. nstep: 1, or up to PM_NSTEP_MAX for n-step targets: the learner then owns a horizon
+        byte per batch row (`horizon`) and row j's target discounts by gamma^horizon[j] (the float32 product
+        chain; pm_dqn_*_n). update_from fills the bytes from the replay's rows; update() takes them as
+        horizon=, or sets every row to nstep."""
         lib = _lib.load()
         batch = int(batch)
         if not 1 <= batch <= PM_MAX_BATCH:
             raise ValueError(f"DQNLearner: batch {batch} (1..{PM_MAX_BATCH})")
         loss, huber_beta, max_norm = (check_option("DQNLearner", k, v) for k, v in
                                       (("loss", loss), ("huber_beta", huber_beta), ("max_norm", max_norm)))
+        nstep = check_nstep("DQNLearner", nstep)
         self.device = torch.device(device)
         params = self._block(modelB)
         z = lambda *shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=self.device)  # noqa: E731
@@ -82,7 +113,8 @@ class DQNLearner:
         norm = z(1) if max_norm is not None else None  # total norm before the clip of the last apply
         self._attach(lib, self.device, buffers, norm, batch=batch, gamma=gamma, lr=lr, betas=betas, eps=eps,
                      target_update_interval=target_update_interval, train_features=train_features,
-                     fresh_noise=fresh_noise, seed=seed, loss=loss, huber_beta=huber_beta, max_norm=max_norm)
+                     fresh_noise=fresh_noise, seed=seed, loss=loss, huber_beta=huber_beta, max_norm=max_norm, nstep=nstep,
+                     horizon=torch.ones(batch, dtype=torch.uint8, device=self.device) if nstep > 1 else None)
 
     @classmethod
     def over(cls, lib, device, buffers, norm, **hyper):
@@ -93,9 +125,12 @@ class DQNLearner:
         return self
 
     def _attach(self, lib, device, buffers, norm, *, batch, gamma, lr, betas, eps, target_update_interval, train_features,
-                fresh_noise, seed, loss, huber_beta, max_norm):
-        """Everything a learner is, given its buffers: the attributes, the descriptor and the options."""
+                fresh_noise, seed, loss, huber_beta, max_norm, nstep=1, horizon=None):
+        """Everything a learner is, given its buffers: the attributes, the descriptor and the options.
+        horizon: the uint8 [batch] horizon buffer, given exactly when nstep > 1."""
         self.lib, self.device, self.batch = lib, device, batch
+        self.nstep, self.horizon = nstep, horizon
+        self.ns_desc = _lib.DqnNstep(horizon=horizon.data_ptr()) if horizon is not None else None
         self.loss, self.huber_beta, self.max_norm, self.train_features = loss, huber_beta, max_norm, bool(train_features)
         for name in BUFFERS:
             setattr(self, name, buffers[name])
@@ -127,8 +162,9 @@ class DQNLearner:
         sd = m.state_dict() if hasattr(m, "state_dict") else m
         return pack_state_dict(sd, self.device)
 
-    def load_batch(self, s, a, r, ns, done, isw=None):
-        """Copy a batch of n <= batch rows (any device / dtype) into the learner's input buffers."""
+    def load_batch(self, s, a, r, ns, done, isw=None, horizon=None):
+        """Copy a batch of n <= batch rows (any device / dtype) into the learner's input buffers. horizon: the
+        rows' horizons (1..PM_NSTEP_MAX) for a learner built with nstep > 1; None sets every row to nstep."""
         s = torch.as_tensor(s)
         n = int(s.reshape(-1, 7).shape[0])
         if not 1 <= n <= self.batch:
@@ -140,21 +176,25 @@ class DQNLearner:
         self.done[:n].copy_(torch.as_tensor(done).reshape(n))
         if isw is not None:
             self.isw[:n].copy_(torch.as_tensor(isw).reshape(n))
+        load_horizon("DQNLearner", self.horizon, self.nstep, n, horizon)
         self.desc.isw = self.isw.data_ptr() if isw is not None else None
         self.desc.batch = n
 
     def _call(self, name, stream=None):
-        if self.opt is None:
+        if self.ns_desc is not None and name != "pm_dqn_apply":  # the apply step has no horizon
+            check(getattr(self.lib, name + "_n")(ctypes.byref(self.desc), ctypes.byref(self.opt) if self.opt else None,
+                                                 ctypes.byref(self.ns_desc), stream_ptr(stream)), name + "_n")
+        elif self.opt is None:
             check(getattr(self.lib, name)(ctypes.byref(self.desc), stream_ptr(stream)), name)
         else:
             check(getattr(self.lib, name + "_opt")(ctypes.byref(self.desc), ctypes.byref(self.opt), stream_ptr(stream)),
                   name + "_opt")
 
-    def update(self, *batch, isw=None, stream=None):
+    def update(self, *batch, isw=None, horizon=None, stream=None):
         """One train_step; batch = (s, a, r, ns, done[, isw]) or nothing (buffers already filled).
         Returns |q - t| per row (a view of the device buffer `td`): update_priorities' errors (:163)."""
         if batch:
-            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
+            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}), horizon=horizon)
         self._call("pm_dqn_update", stream)
         return self.td[:self.desc.batch]
 
@@ -165,7 +205,10 @@ class DQNLearner:
         back with the sum tree refreshed where they changed — no host synchronisation, and the replay's
         tree stays current (no refresh() needed). uniforms: float64 [updates, batch] to replay given
         draws; None draws u53(Philox(j, TAG_PER, frame, seed)). Returns (idx, td) of the last update as
-        device tensors (views of `idx` / `td`; idx is -1 where that update was void, see stats()["status"])."""
+        device tensors (views of `idx` / `td`; idx is -1 where that update was void, see stats()["status"]).
+        A learner built with nstep > 1 reads every drawn row's own horizon (pm_dqn_replay_update_n); one built with
+        nstep=1 raises PongmiError on a replay that holds longer horizons."""
+        check_replay_horizon("DQNLearner.update_from", replay, self.nstep)
         n = self.batch
         updates = int(updates)
         u = None
@@ -179,7 +222,11 @@ class DQNLearner:
                             idx=self.idx.data_ptr(), u=u.data_ptr() if u is not None else None, cap=replay.cap,
                             size=replay.size, alpha=replay.alpha, beta_start=float(beta_start),
                             beta_frames=int(beta_frames), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-        if self.opt is None:
+        if self.ns_desc is not None:
+            check(self.lib.pm_dqn_replay_update_n(ctypes.byref(self.desc), ctypes.byref(self.opt) if self.opt else None,
+                                                  ctypes.byref(self.ns_desc), ctypes.byref(rp), updates,
+                                                  stream_ptr(stream)), "pm_dqn_replay_update_n")
+        elif self.opt is None:
             check(self.lib.pm_dqn_replay_update(ctypes.byref(self.desc), ctypes.byref(rp), updates, stream_ptr(stream)),
                   "pm_dqn_replay_update")
         else:
@@ -188,9 +235,9 @@ class DQNLearner:
         replay.max_prio_stale = True
         return self.idx[:n], self.td[:n]
 
-    def grads(self, *batch, isw=None, stream=None):
+    def grads(self, *batch, isw=None, horizon=None, stream=None):
         if batch:
-            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}))
+            self.load_batch(*batch, **({"isw": isw} if isw is not None else {}), horizon=horizon)
         self._call("pm_dqn_grads", stream)
         return self.td[:self.desc.batch]
 
@@ -272,8 +319,13 @@ class ReplayTrainer:
     nothing else; the stats are summed on the device and read once at the end."""
 
     def __init__(self, env, wA, learner, replay, *, collect_steps, updates, epsilon=0.02, seed_net=0, beta_start=0.4,
-                 beta_frames=100000, seed=0):
+                 beta_frames=100000, seed=0, nstep=None):
+        """nstep: the collector's window (None: the learner's nstep). The collector discounts by the learner's gamma;
+        a window above 1 needs a learner built with nstep > 1."""
         from .rollout import SelfPlayRollout
+        self.nstep = learner.nstep if nstep is None else check_nstep("ReplayTrainer", nstep)
+        if self.nstep > 1 and learner.nstep == 1:
+            raise ValueError(f"ReplayTrainer: nstep {self.nstep} with a learner built with nstep=1")
         self.learner, self.replay = learner, replay
         self.collect_steps, self.updates = int(collect_steps), int(updates)
         if self.collect_steps < 1 or self.updates < 1:
@@ -287,7 +339,8 @@ class ReplayTrainer:
         from .rollout import STATS_PUSH
         total = torch.zeros_like(self.rollout.stats)
         for _ in range(int(iterations)):
-            total += self.rollout.run(self.collect_steps, replay=self.replay, sync=False)
+            total += self.rollout.run(self.collect_steps, replay=self.replay, sync=False, nstep=self.nstep,
+                                      gamma=self.learner.desc.gamma)
             self.learner.update_from(self.replay, self.updates, beta_start=self.beta_start,
                                      beta_frames=self.beta_frames, seed=self.seed)
             self.rollout.set_paramsB(self.learner.params)
@@ -311,8 +364,17 @@ class PopulationTrainer:
     a run() performs no host synchronisation until that final read."""
 
     def __init__(self, env, wA, population, replays, *, collect_steps, updates, epsilon=0.02, seed_env=None, seed_net=0,
-                 beta_start=0.4, beta_frames=100000, seed=0):
+                 beta_start=0.4, beta_frames=100000, seed=0, nstep=None):
+        """nstep: the collectors' windows, one value or n (None: the members' own nstep). Member p's collector
+        discounts by member p's gamma; a window above 1 needs a member built with nstep > 1."""
+        from ._pop import per_member
         from .rollout import PopulationRollout
+        own = list(getattr(population, "nstep", [1] * population.n))  # a population without the attribute: one step
+        self.nstep = own if nstep is None else \
+            [check_nstep("PopulationTrainer", x) for x in per_member("PopulationTrainer", "nstep", nstep, population.n)]
+        for p, k in enumerate(self.nstep):
+            if k > 1 and own[p] == 1:
+                raise ValueError(f"PopulationTrainer: member {p}: nstep {k} with a member built with nstep=1")
         self.population, self.replays = population, list(replays)
         self.collect_steps, self.updates = int(collect_steps), int(updates)
         if self.collect_steps < 1 or self.updates < 1:
@@ -320,7 +382,8 @@ class PopulationTrainer:
         self.beta_start, self.beta_frames, self.seed = float(beta_start), int(beta_frames), seed
         self.rollout = PopulationRollout(env, wA, population.params, n=population.n, replays=self.replays,
                                          epsilon=epsilon, seed_env=seed_env, seed_net=seed_net,
-                                         steps_max=self.collect_steps)
+                                         steps_max=self.collect_steps, nstep=self.nstep,
+                                         gamma=population.hyper["gamma"] if max(self.nstep) > 1 else 0.99)
 
     def run(self, iterations):
         from .rollout import STATS_PUSH

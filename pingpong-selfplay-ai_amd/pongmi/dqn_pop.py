@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from ._lib import PM_DQN_NPARAM, PM_DQN_POP_MAX, PM_MAX_BATCH, PM_QNET_NP, check, stream_ptr
 from ._pop import TableHandle, per_member
-from .dqn import BUFFERS, DQNLearner, check_option
+from .dqn import BUFFERS, DQNLearner, check_nstep, check_option, check_replay_horizon, load_horizon
 from .qnet import fold, unpack_state_dict
 
 PER_MEMBER = ("gamma", "lr", "betas", "eps", "target_update_interval", "train_features", "fresh_noise", "seed", "loss",
@@ -61,13 +61,15 @@ class DQNPopulation(TableHandle):
 
     def __init__(self, models, targets=None, *, n=None, batch=256, device="cuda", shared_batch=False, gamma=0.99,
                  lr=2.5e-4, betas=(0.9, 0.999), eps=1e-8, target_update_interval=1000, train_features=False,
-                 fresh_noise=True, seed=0, loss="mse", huber_beta=1.0, max_norm=None):
+                 fresh_noise=True, seed=0, loss="mse", huber_beta=1.0, max_norm=None, nstep=1):
         """models / targets: a sequence of n QNet modules, state_dicts or packed [PM_QNET_NP] tensors, a stacked
         [n, PM_QNET_NP] tensor, or ONE of them with n given (every member starts from a copy); targets None =
         copies of models. batch: the most rows an update takes (1..256). It and every other keyword of
         DQNLearner's are given as one value for all members or as a sequence of n (the stacked batch buffers
-        have max(batch) rows; update_from draws batch[p] rows for member p). Bad values raise ValueError
-        before anything is allocated."""
+        have max(batch) rows; update_from draws batch[p] rows for member p). nstep: one value or n, as
+        DQNLearner's: members with nstep > 1 get a row of the stacked `horizon` bytes [n, batch]
+        (pm_dqn_nstep_pop_set), the others keep the one-step target. Bad values raise ValueError before anything
+        is allocated."""
         many = isinstance(models, (list, tuple)) or (isinstance(models, torch.Tensor) and models.dim() == 2)
         if n is None:
             if not many:
@@ -92,6 +94,7 @@ class DQNPopulation(TableHandle):
                      train_features=train_features, fresh_noise=fresh_noise, seed=seed, loss=loss, huber_beta=huber_beta,
                      max_norm=max_norm)
         self.hyper = {k: [_validate(k, v) for v in _per_member(k, given[k], n, k == "betas")] for k in PER_MEMBER}
+        self.nstep = [check_nstep("DQNPopulation", v) for v in _per_member("nstep", nstep, n)]
         # ---- nothing above allocates
         self.lib = _lib.load()
         self.n, self.shared_batch = n, bool(shared_batch)
@@ -115,6 +118,12 @@ class DQNPopulation(TableHandle):
         self.q = torch.zeros((n, B, 3), **f32)
         self.idx = torch.zeros((n, B), dtype=torch.int64, device=self.device)  # update_from's sampled slots
         self.norm = torch.zeros(n, **f32)  # every member's total gradient norm before the clip of its last apply
+        # the members' horizon bytes (rows of their own even with shared_batch: the replay gather writes them)
+        self.horizon = torch.ones((n, B), dtype=torch.uint8, device=self.device) if max(self.nstep) > 1 else None
+        self._ns = (_lib.DqnNstep * n)()
+        for p in range(n):
+            self._ns[p].horizon = self.horizon[p].data_ptr() if self.nstep[p] > 1 else None
+        self._ns_set = self.horizon is None  # the handle's horizon buffers are _ns (none at create)
         self._d = (_lib.Dqn * n)()
         self._o = (_lib.DqnOpt * n)()
         for p in range(n):
@@ -170,7 +179,7 @@ class DQNPopulation(TableHandle):
         self._write_hyper()
 
     # ------------------------------------------------------------------ batches
-    def _load(self, p, s, a, r, ns, done, isw):
+    def _load(self, p, s, a, r, ns, done, isw, horizon=None):
         s = torch.as_tensor(s)
         rows = int(s.reshape(-1, 7).shape[0])
         cap = self.batch if p is None else self.batches[p]
@@ -187,23 +196,27 @@ class DQNPopulation(TableHandle):
         for q in (range(self.n) if self.shared_batch else (p,)):
             self._d[q].isw = pick(self.isw).data_ptr() if isw is not None else None
             self._d[q].batch = rows
+            load_horizon("DQNPopulation", self.horizon[q] if self.nstep[q] > 1 else None, self.nstep[q], rows,
+                         horizon if self.nstep[q] > 1 or not self.shared_batch else None)
 
-    def load_batch(self, member, s, a, r, ns, done, isw=None):
+    def load_batch(self, member, s, a, r, ns, done, isw=None, horizon=None):
         """Copy rows <= batch rows (any device / dtype) into one member's input buffers; with shared_batch into
-        the one set every member reads (`member` is then ignored)."""
+        the one set every member reads (`member` is then ignored). horizon: the rows' horizons for members built
+        with nstep > 1 (None: the member's nstep for every row)."""
         if not self.shared_batch and not 0 <= int(member) < self.n:
             raise ValueError(f"DQNPopulation: member {member} (0..{self.n - 1})")
-        self._load(None if self.shared_batch else int(member), s, a, r, ns, done, isw)
+        self._load(None if self.shared_batch else int(member), s, a, r, ns, done, isw, horizon)
 
-    def load_batches(self, s, a, r, ns, done, isw=None):
+    def load_batches(self, s, a, r, ns, done, isw=None, horizon=None):
         """Stacked inputs, [n, rows, ...] (the same row count for every member); with shared_batch [rows, ...]."""
         if self.shared_batch:
-            return self._load(None, s, a, r, ns, done, isw)
+            return self._load(None, s, a, r, ns, done, isw, horizon)
         s, a, r, ns, done = (torch.as_tensor(x) for x in (s, a, r, ns, done))
         if s.shape[0] != self.n:
             raise ValueError(f"DQNPopulation: {s.shape[0]} stacked batches for {self.n} members")
         for p in range(self.n):
-            self._load(p, s[p], a[p], r[p], ns[p], done[p], None if isw is None else torch.as_tensor(isw)[p])
+            self._load(p, s[p], a[p], r[p], ns[p], done[p], None if isw is None else torch.as_tensor(isw)[p],
+                       None if horizon is None else torch.as_tensor(horizon)[p])
 
     def rows(self):
         """The row count each member's next update() takes."""
@@ -215,6 +228,9 @@ class DQNPopulation(TableHandle):
         want = (bytes(self._d), bytes(self._o), bytes(rp) if rp is not None else None)
         self._table(want != self._bound, (self._d, self._o, rp, self.n), (self._d, self._o, rp, stream_ptr(stream)))
         self._bound = want
+        if not self._ns_set:
+            check(self.lib.pm_dqn_nstep_pop_set(self._handle, self._ns, stream_ptr(stream)), "pm_dqn_nstep_pop_set")
+            self._ns_set = True
 
     def update(self, stream=None):
         """One train_step of every member on the batch its buffers hold, as one launch. Returns td [n, batch]
@@ -243,6 +259,8 @@ class DQNPopulation(TableHandle):
         replays = list(replays)
         if len(replays) != n:
             raise ValueError(f"DQNPopulation.update_from: {len(replays)} replays for {n} members")
+        for p, r in enumerate(replays):
+            check_replay_horizon(f"DQNPopulation.update_from: member {p}", r, self.nstep[p])
         updates = int(updates)
         seeds = [int(x) & 0xFFFFFFFFFFFFFFFF for x in _per_member("seed", seed, n)]
         u = None
@@ -312,7 +330,8 @@ class DQNPopulation(TableHandle):
             t = t if self.shared_batch and name in ("s", "ns", "act", "rew", "done", "isw") else t[i]
             buffers[name] = t if name in ("params", "target", "adam_m", "adam_v", "grad", "stats_buf") else t[:batch]
         L = DQNLearner.over(self.lib, self.device, buffers, self.norm[i:i + 1] if h["max_norm"] is not None else None,
-                            batch=batch, **h)
+                            batch=batch, nstep=self.nstep[i],
+                            horizon=self.horizon[i][:batch] if self.nstep[i] > 1 else None, **h)
         L.desc.isw, L.desc.batch = self._d[i].isw, self._d[i].batch  # as the table has them now
         return L
 

@@ -52,7 +52,10 @@ class DeviceReplay:
     while empty, :57) — pushes never change it, so it is tracked here; call refresh() after
     changing prios by other means (it also rebuilds the sum tree). push() adds the caller's own
     transitions (pm_replay_push); DQNLearner.update_from trains from the ring and keeps the tree
-    current itself (it marks max_prio stale, and the next push_prio() re-reads it)."""
+    current itself (it marks max_prio stale, and the next push_prio() re-reads it).
+    A row carries its own n-step horizon (1..PM_NSTEP_MAX, as k - 1 in bits 16..18 of its last word; rows
+    pushed without one are one step). max_horizon is the largest ever pushed into this ring, by push(horizon=)
+    or by an n-step collector: a learner built with nstep=1 refuses a ring where it is above 1."""
 
     def __init__(self, cap, device, alpha=0.6):
         self.cap = int(cap)
@@ -67,6 +70,7 @@ class DeviceReplay:
         self.size = 0
         self.max_prio = 1.0
         self.max_prio_stale = False  # set by DQNLearner.update_from: prios changed on the device
+        self.max_horizon = 1
 
     def push_prio(self):
         """The priority the next push stores. After DQNLearner.update_from changed prios on the device the
@@ -80,11 +84,13 @@ class DeviceReplay:
         self.pos = (self.pos + pushed) % self.cap
         self.size = min(self.cap, self.size + pushed)
 
-    def push(self, s, a, r, ns, done, stream=None):
+    def push(self, s, a, r, ns, done, stream=None, horizon=None):
         """memory.push (:56-63) of n <= cap transitions of the caller's (tensors or arrays of any device /
         dtype: s, ns [n, 7]; a in 0..2, r, done [n]) at pos with push_prio() as their priority
         (pm_replay_push); the sum tree stays current. Actions are checked where the host sees them (inputs
-        not on the device)."""
+        not on the device). horizon: None (one-step rows), or [n] values in 1..PM_NSTEP_MAX for the caller's own
+        n-step rows (r then the n-step reward, ns the state after the last of the row's ticks; pm_replay_push_n).
+        Its maximum is read on the host (a sync where it is a device tensor)."""
         dev = self.trans.device
         s = torch.as_tensor(s)
         n = int(s.reshape(-1, 7).shape[0])
@@ -99,10 +105,22 @@ class DeviceReplay:
         r = torch.as_tensor(r).reshape(n).to(**f32).contiguous()
         a = a.to(device=dev, dtype=torch.int32).contiguous()
         done = torch.as_tensor(done).reshape(n).to(device=dev, dtype=torch.uint8).contiguous()
+        if horizon is not None:
+            horizon = torch.as_tensor(horizon).reshape(n)
+            lo, hi = int(horizon.min()), int(horizon.max())
+            if lo < 1 or hi > _lib.PM_NSTEP_MAX:
+                raise ValueError(f"DeviceReplay.push: horizons must be 1..{_lib.PM_NSTEP_MAX}")
+            horizon = horizon.to(device=dev, dtype=torch.uint8).contiguous()
         prio = self.push_prio()
-        check(_lib.load().pm_replay_push(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos, self.alpha,
-                                         prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done), n, stream_ptr(stream)),
-              "pm_replay_push")
+        if horizon is None:
+            check(_lib.load().pm_replay_push(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos,
+                                             self.alpha, prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done), n,
+                                             stream_ptr(stream)), "pm_replay_push")
+        else:
+            check(_lib.load().pm_replay_push_n(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos,
+                                               self.alpha, prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done),
+                                               ptr(horizon), n, stream_ptr(stream)), "pm_replay_push_n")
+            self.max_horizon = max(self.max_horizon, hi)
         if self.size == 0:
             self.max_prio = 1.0
         self.advance(n)

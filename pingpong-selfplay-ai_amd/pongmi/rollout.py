@@ -20,8 +20,10 @@ loop's memory.push((oB, aB, rB, nB, done)) (:242-243) — the rows go from regis
 the launch leaves the PER sum tree current — with ep_reward carried per arena (:245) and the stats
 gaining the loop's episode wins (ep_reward > 0, :247) and reward sum.
 """
+import math
 from functools import partial
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -31,6 +33,44 @@ from .env import ctypes_ref
 
 STATS = ("episodes", "wins_B", "points_A", "points_B")
 STATS_PUSH = STATS + ("wins_B_episode", "reward_B")
+
+
+def nstep_fold_host(rows_1step, n, steps, N, gamma):
+    """The host model of the n-step collector (pm_rollout_push_n): the rows a launch of `steps` vector steps over n
+    arenas writes with a window of N ticks, from the rows the one-step launch writes. rows_1step: float32
+    [steps * n, PM_TRANS_F] in launch order (row st * n + i is step st's arena i; unwrap a ring first). Returns
+    the same shape: row st * n + i is the transition opened at step st with its n-step reward, the s' and done of
+    the tick that closed it, and its horizon k as k - 1 in bits 16..18 of the last word. Everything is float32
+    in the device's order: per tick R = R + f * r, then f = f * g, from (0, 1). N = 1 returns the input."""
+    rows = np.ascontiguousarray(rows_1step, dtype=np.float32).reshape(int(steps), int(n), _lib.PM_TRANS_F)
+    N = int(N)
+    if not 1 <= N <= _lib.PM_NSTEP_MAX:
+        raise ValueError(f"nstep_fold_host: N {N} (1..{_lib.PM_NSTEP_MAX})")
+    out = rows.copy()
+    if N == 1:
+        return out.reshape(-1, _lib.PM_TRANS_F)
+    bits, obits = rows[:, :, 15].view(np.int32), out[:, :, 15].view(np.int32)
+    g = np.float32(gamma)
+    for i in range(int(n)):
+        pending = []  # [opening step, R, f, k]
+        for st in range(int(steps)):
+            r, done = rows[st, i, 7], int(bits[st, i] >> 8) & 1
+            pending.append([st, np.float32(0), np.float32(1), 0])
+            for e in pending:
+                e[1] = np.float32(e[1] + np.float32(e[2] * r))
+                e[2] = np.float32(e[2] * g)
+                e[3] += 1
+            keep = []
+            for e in pending:
+                t, R, _, k = e
+                if done or st == steps - 1 or k == N:
+                    out[t, i, 7] = R
+                    out[t, i, 8:15] = rows[st, i, 8:15]
+                    obits[t, i] = (int(bits[t, i]) & ~0x70100) | (done << 8) | ((k - 1) << 16)
+                else:
+                    keep.append(e)
+            pending = keep
+    return out.reshape(-1, _lib.PM_TRANS_F)
 
 
 class SelfPlayRollout:
@@ -70,9 +110,32 @@ class SelfPlayRollout:
         if self.heads.numel() < int(steps) * PM_ROLL_HEADS:
             self.heads = torch.empty(int(steps) * PM_ROLL_HEADS, dtype=torch.float32, device=self.env.device)
 
-    def run(self, steps, sync=True, replay=None):
+    def _push(self, steps, replay, nstep, gamma):
+        """The collecting launch: pm_rollout_push, or with an nstep (1 included) pm_rollout_push_n."""
+        env = self.env
+        rp = _lib.RollReplay(trans=ptr(replay.trans), prios=ptr(replay.prios), per_work=ptr(replay.work),
+                             ep_reward=ptr(self.ep_reward), pos=replay.pos, cap=replay.cap,
+                             prio=replay.push_prio(), alpha=replay.alpha)
+        args = (ctypes_ref(env.params), ctypes_ref(env.state), ptr(self.wA), ptr(self.wB), ptr(self.paramsB),
+                self.epsilon, env.seed, self.seed_net, env.counter, steps, ptr(self.heads), ptr(env.obsA),
+                ptr(env.obsB), ctypes_ref(rp), ptr(self.stats), env.n)
+        if nstep is None:
+            check(self.lib.pm_rollout_push(*args, stream_ptr()), "pm_rollout_push")
+        else:
+            check(self.lib.pm_rollout_push_n(*args, int(nstep), float(gamma), stream_ptr()), "pm_rollout_push_n")
+            replay.max_horizon = max(replay.max_horizon, int(nstep))
+        if steps and env.n:
+            if replay.size == 0:
+                replay.max_prio = 1.0
+            replay.advance(steps * env.n)
+
+    def run(self, steps, sync=True, replay=None, nstep=1, gamma=0.99):
         """replay: None (inference only, pm_rollout) or a DeviceReplay the launch pushes every step's
-        transitions into (pm_rollout_push; steps * n <= replay.cap)."""
+        transitions into (pm_rollout_push; steps * n <= replay.cap). nstep > 1 (up to PM_NSTEP_MAX), with a
+        replay: the rows are n-step transitions over a window of nstep ticks discounted by gamma
+        (pm_rollout_push_n; nstep_fold_host is the model). The window is per launch: transitions still pending
+        after the last step are written with their shorter horizon. The trajectory and the stats do not depend
+        on nstep."""
         steps = int(steps)
         if steps < 0:
             raise ValueError("steps must be >= 0")
@@ -87,17 +150,7 @@ class SelfPlayRollout:
                                       stream_ptr()), "pm_rollout")
         else:
             names = STATS_PUSH
-            rp = _lib.RollReplay(trans=ptr(replay.trans), prios=ptr(replay.prios), per_work=ptr(replay.work),
-                                 ep_reward=ptr(self.ep_reward), pos=replay.pos, cap=replay.cap,
-                                 prio=replay.push_prio(), alpha=replay.alpha)
-            check(self.lib.pm_rollout_push(ctypes_ref(env.params), ctypes_ref(env.state), ptr(self.wA), ptr(self.wB),
-                                           ptr(self.paramsB), self.epsilon, env.seed, self.seed_net, env.counter,
-                                           steps, ptr(self.heads), ptr(env.obsA), ptr(env.obsB), ctypes_ref(rp),
-                                           ptr(self.stats), env.n, stream_ptr()), "pm_rollout_push")
-            if steps and env.n:
-                if replay.size == 0:
-                    replay.max_prio = 1.0
-                replay.advance(steps * env.n)
+            self._push(steps, replay, None if int(nstep) == 1 else nstep, gamma)
         env.counter += steps
         if not sync:
             return self.stats
@@ -137,6 +190,8 @@ class PopulationRollout(TableHandle):
               device): pass DQNPopulation.params and every collect plays what the learners hold, with no copy.
     replays   n distinct DeviceReplays, cap >= steps_max * m each; one whose `work` is None keeps no sum tree.
     epsilon, seed_env, seed_net   one value or n values; seed_env None = env.seed + p.
+    nstep, gamma   one value or n values: member p collects n-step rows as SelfPlayRollout.run(nstep=nstep[p],
+              gamma=gamma[p]) does (pm_rollout_nstep_pop_set); all ones (the default) is the one-step launch.
     steps_max the most vector steps one collect takes (default: min(32, min(cap) // m)).
     Bad values raise ValueError before anything is allocated.
 
@@ -149,8 +204,8 @@ class PopulationRollout(TableHandle):
     (someone else pushed into it) or one of its buffers was replaced."""
     _entry = "pm_rollout_pop"
 
-    def __init__(self, env, wA, params, *, n, replays, epsilon=0.02, seed_env=None, seed_net=0, steps_max=None):
-        import math
+    def __init__(self, env, wA, params, *, n, replays, epsilon=0.02, seed_env=None, seed_net=0, steps_max=None,
+                 nstep=1, gamma=0.99):
         n = int(n)
         if not 1 <= n <= _lib.PM_DQN_POP_MAX:
             raise ValueError(f"PopulationRollout: n {n} (1..{_lib.PM_DQN_POP_MAX})")
@@ -178,6 +233,13 @@ class PopulationRollout(TableHandle):
         for p, x in enumerate(eps):
             if not math.isfinite(x):
                 raise ValueError(f"PopulationRollout: member {p}: epsilon {x}")
+        nsteps = [int(x) for x in _per_member("nstep", nstep, n)]
+        gammas = [float(x) for x in _per_member("gamma", gamma, n)]
+        for p in range(n):
+            if not 1 <= nsteps[p] <= _lib.PM_NSTEP_MAX:
+                raise ValueError(f"PopulationRollout: member {p}: nstep {nsteps[p]} (1..{_lib.PM_NSTEP_MAX})")
+            if not math.isfinite(gammas[p]):
+                raise ValueError(f"PopulationRollout: member {p}: gamma {gammas[p]}")
         mask = 0xFFFFFFFFFFFFFFFF
         if seed_env is None:
             seed_env = [env.seed + p for p in range(n)]
@@ -201,6 +263,8 @@ class PopulationRollout(TableHandle):
         self.lib = _lib.load()
         self.env, self.n, self.m, self.steps_max = env, n, m, steps_max
         self.params, self.replays, self.epsilon = params, replays, eps
+        self.nstep, self.gamma = nsteps, gammas
+        self._nstep_set = max(nsteps) == 1  # the handle's horizons are what self.nstep says (all ones at create)
         dev = env.device
         if isinstance(wA, (list, tuple)):
             own = {id(t): _weights(t, PM_QNET_NW, "wA", dev) for t in wA}
@@ -245,6 +309,11 @@ class PopulationRollout(TableHandle):
         self._table(True, (ctypes_ref(self.env.params), ctypes_ref(self.env.state), self._members, self.n, self.m,
                            self.steps_max), (self._members, stream))
         self._advance, self._left, self._bufs = 0, left, bufs
+        if not self._nstep_set:
+            check(self.lib.pm_rollout_nstep_pop_set(self._handle, (_lib.c_i32 * self.n)(*self.nstep),
+                                                    (_lib.c_double * self.n)(*self.gamma), stream),
+                  "pm_rollout_nstep_pop_set")
+            self._nstep_set = True
 
     def collect(self, steps, sync=True):
         """`steps` vector steps of every member (0..steps_max). Returns the call's stats as a dict of STATS_PUSH
@@ -263,9 +332,10 @@ class PopulationRollout(TableHandle):
                                                ptr(env.obsB), st), "pm_rollout_pop_push")
             pushed = steps * self.m
             self._advance += pushed
-            for r in self.replays:
+            for p, r in enumerate(self.replays):
                 r.advance(pushed)
                 r.max_prio_stale = True
+                r.max_horizon = max(r.max_horizon, self.nstep[p])
             self._left = [(r.pos, r.size) for r in self.replays]
             env.counter += steps
         if not sync:
