@@ -447,7 +447,9 @@ __global__ __launch_bounds__(kDqn, 1) void k_dqn_apply(const pm_dqn d) {
 }
 
 // pm_dqn_update: both in one launch, the gradient handed over through grad (the same loads and the same
-// arithmetic as the two launches: bit-identical).
+// arithmetic as the two launches: bit-identical). The eight update kernels below spell their LDS blocks and their two
+// body calls out one by one on purpose: behind one shared dqn_update_body<kOpt, kN> every one of them compiled to
+// different text (17 to 27 lines, the same counts and resources), so the wrappers stay as they are.
 __global__ __launch_bounds__(kDqn, 1) void k_dqn_update(const pm_dqn d) {
     __shared__ __attribute__((aligned(16))) DqnSmem sm;
     __shared__ float ak[2];
@@ -576,119 +578,85 @@ pm_dqn_opt opt_or_default(const pm_dqn_opt* o) {
     return o ? *o : z;
 }
 
-int dqn_grads(const pm_dqn* d, void* stream) {
-    hipLaunchKernelGGL(k_dqn_grads, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d);
-    PM_LAUNCHED("k_dqn_grads");
-    return PM_OK;
-}
-
-int dqn_apply(const pm_dqn* d, void* stream) {
-    hipLaunchKernelGGL(k_dqn_apply, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d);
-    PM_LAUNCHED("k_dqn_apply");
-    return PM_OK;
-}
-
 }  // namespace
 
-int dqn_check(const pm_dqn* d) { return check(d); }
-
-int dqn_launch_update_gated(const pm_dqn* d, const int64_t* gate, hipStream_t st) {
-    hipLaunchKernelGGL(k_dqr_update, dim3(1), dim3(kDqn), 0, st, *d, gate);
-    PM_LAUNCHED("k_dqr_update");
-    return PM_OK;
+int dqn_check(const pm_dqn* d, const pm_dqn_opt* o) {
+    if (int rc = check(d)) return rc;
+    return check_opt(o);
 }
 
-int dqn_check_opt(const pm_dqn_opt* o) { return check_opt(o); }
-
-int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int64_t* gate, hipStream_t st) {
-    hipLaunchKernelGGL(k_dqr_update_opt, dim3(1), dim3(kDqn), 0, st, *d, opt_or_default(o), gate);
-    PM_LAUNCHED("k_dqr_update_opt");
-    return PM_OK;
-}
-
-int dqn_launch_update_gated_n(const pm_dqn* d, const pm_dqn_opt* o, const uint8_t* hz, const int64_t* gate,
-                              hipStream_t st) {
-    hipLaunchKernelGGL(k_dqr_update_n, dim3(1), dim3(kDqn), 0, st, *d, opt_or_default(o), hz, gate);
-    PM_LAUNCHED("k_dqr_update_n");
-    return PM_OK;
-}
-
-int dqp_launch_update(const pm_dqn_member* tab, const uint8_t* const* hzt, int n, int gated, hipStream_t st) {
-    if (hzt) {
-        hipLaunchKernelGGL(k_dqp_update_n, dim3(n), dim3(kDqn), 0, st, tab, hzt, gated);
-        PM_LAUNCHED("k_dqp_update_n");
-        return PM_OK;
+// The one place where a stand-alone learner's kernel is chosen: the plain ones without an options record, the _opt
+// ones with one (a null record is the defaults), the _n ones with one and a horizon buffer. The apply stage reads no
+// horizon and has no _n form.
+int dqn_launch(DqnStage stage, const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const uint8_t* hz,
+               const int64_t* gate, hipStream_t st) {
+    const pm_dqn_opt op = opt_or_default(o);
+    const char* name;
+    const auto launch = [&](auto kernel, const char* kernel_name, auto... more) {
+        hipLaunchKernelGGL(kernel, dim3(1), dim3(kDqn), 0, st, *d, more...);
+        name = kernel_name;
+    };
+#define K(kernel) kernel, #kernel
+    switch (3 * stage + (!with_opt ? 0 : hz && stage != DQN_APPLY ? 2 : 1)) {
+        case 3 * DQN_GRADS + 0: launch(K(k_dqn_grads)); break;
+        case 3 * DQN_GRADS + 1: launch(K(k_dqn_grads_opt), op); break;
+        case 3 * DQN_GRADS + 2: launch(K(k_dqn_grads_n), op, hz); break;
+        case 3 * DQN_APPLY + 0: launch(K(k_dqn_apply)); break;
+        case 3 * DQN_APPLY + 1: launch(K(k_dqn_apply_opt), op); break;
+        case 3 * DQN_UPDATE + 0: launch(K(k_dqn_update)); break;
+        case 3 * DQN_UPDATE + 1: launch(K(k_dqn_update_opt), op); break;
+        case 3 * DQN_UPDATE + 2: launch(K(k_dqn_update_n), op, hz); break;
+        case 3 * DQN_UPDATE_GATED + 0: launch(K(k_dqr_update), gate); break;
+        case 3 * DQN_UPDATE_GATED + 1: launch(K(k_dqr_update_opt), op, gate); break;
+        case 3 * DQN_UPDATE_GATED + 2: launch(K(k_dqr_update_n), op, hz, gate); break;
+        default: return pm_fail(PM_E_ARG, "dqn_launch: stage %d", (int)stage);
     }
-    hipLaunchKernelGGL(k_dqp_update, dim3(n), dim3(kDqn), 0, st, tab, gated);
-    PM_LAUNCHED("k_dqp_update");
+#undef K
+    PM_LAUNCHED(name);
+    return PM_OK;
+}
+
+// The population's update picks by the same rule: the _n kernel with a table of horizon buffers.
+int dqp_launch_update(const pm_dqn_member* tab, const uint8_t* const* hzt, int n, int gated, hipStream_t st) {
+    if (hzt)
+        hipLaunchKernelGGL(k_dqp_update_n, dim3(n), dim3(kDqn), 0, st, tab, hzt, gated);
+    else
+        hipLaunchKernelGGL(k_dqp_update, dim3(n), dim3(kDqn), 0, st, tab, gated);
+    PM_LAUNCHED(hzt ? "k_dqp_update_n" : "k_dqp_update");
     return PM_OK;
 }
 }  // namespace pm
 
 using namespace pm;
 
-extern "C" int pm_dqn_grads(const pm_dqn* d, void* stream) {
-    if (int rc = check(d)) return rc;
-    return dqn_grads(d, stream);
-}
-
-extern "C" int pm_dqn_apply(const pm_dqn* d, void* stream) {
-    if (int rc = check(d)) return rc;
-    return dqn_apply(d, stream);
-}
-
-extern "C" int pm_dqn_update(const pm_dqn* d, void* stream) {
-    if (int rc = check(d)) return rc;
-    hipLaunchKernelGGL(k_dqn_update, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d);
-    PM_LAUNCHED("k_dqn_update");
-    return PM_OK;
+// Every pm_dqn_* entry below: the checks, then the launch. with_opt false: the plain kernels; a null pm_dqn_nstep, or
+// one with a null horizon, is the _opt entry as it is (the same kernel).
+static int dqn_entry(DqnStage stage, const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const pm_dqn_nstep* ns,
+                     void* stream) {
+    if (int rc = dqn_check(d, o)) return rc;
+    return dqn_launch(stage, d, with_opt, o, ns ? ns->horizon : nullptr, nullptr, pm_stream(stream));
 }
 
 extern "C" size_t pm_dqn_opt_sizeof(void) { return sizeof(pm_dqn_opt); }
-
-extern "C" int pm_dqn_grads_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
-    if (int rc = check(d)) return rc;
-    if (int rc = check_opt(o)) return rc;
-    hipLaunchKernelGGL(k_dqn_grads_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
-    PM_LAUNCHED("k_dqn_grads_opt");
-    return PM_OK;
-}
-
-extern "C" int pm_dqn_apply_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
-    if (int rc = check(d)) return rc;
-    if (int rc = check_opt(o)) return rc;
-    hipLaunchKernelGGL(k_dqn_apply_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
-    PM_LAUNCHED("k_dqn_apply_opt");
-    return PM_OK;
-}
-
-extern "C" int pm_dqn_update_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
-    if (int rc = check(d)) return rc;
-    if (int rc = check_opt(o)) return rc;
-    hipLaunchKernelGGL(k_dqn_update_opt, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o));
-    PM_LAUNCHED("k_dqn_update_opt");
-    return PM_OK;
-}
-
 extern "C" size_t pm_dqn_nstep_sizeof(void) { return sizeof(pm_dqn_nstep); }
 
-// A null pm_dqn_nstep, or one with a null horizon, is the _opt entry as it is (the same kernel).
-extern "C" int pm_dqn_grads_n(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_nstep* ns, void* stream) {
-    if (!ns || !ns->horizon) return pm_dqn_grads_opt(d, o, stream);
-    if (int rc = check(d)) return rc;
-    if (int rc = check_opt(o)) return rc;
-    hipLaunchKernelGGL(k_dqn_grads_n, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o),
-                       (const uint8_t*)ns->horizon);
-    PM_LAUNCHED("k_dqn_grads_n");
-    return PM_OK;
+extern "C" int pm_dqn_grads(const pm_dqn* d, void* stream) { return dqn_entry(DQN_GRADS, d, false, nullptr, nullptr, stream); }
+extern "C" int pm_dqn_apply(const pm_dqn* d, void* stream) { return dqn_entry(DQN_APPLY, d, false, nullptr, nullptr, stream); }
+extern "C" int pm_dqn_update(const pm_dqn* d, void* stream) { return dqn_entry(DQN_UPDATE, d, false, nullptr, nullptr, stream); }
+
+extern "C" int pm_dqn_grads_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    return dqn_entry(DQN_GRADS, d, true, o, nullptr, stream);
+}
+extern "C" int pm_dqn_apply_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    return dqn_entry(DQN_APPLY, d, true, o, nullptr, stream);
+}
+extern "C" int pm_dqn_update_opt(const pm_dqn* d, const pm_dqn_opt* o, void* stream) {
+    return dqn_entry(DQN_UPDATE, d, true, o, nullptr, stream);
 }
 
+extern "C" int pm_dqn_grads_n(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_nstep* ns, void* stream) {
+    return dqn_entry(DQN_GRADS, d, true, o, ns, stream);
+}
 extern "C" int pm_dqn_update_n(const pm_dqn* d, const pm_dqn_opt* o, const pm_dqn_nstep* ns, void* stream) {
-    if (!ns || !ns->horizon) return pm_dqn_update_opt(d, o, stream);
-    if (int rc = check(d)) return rc;
-    if (int rc = check_opt(o)) return rc;
-    hipLaunchKernelGGL(k_dqn_update_n, dim3(1), dim3(kDqn), 0, pm_stream(stream), *d, opt_or_default(o),
-                       (const uint8_t*)ns->horizon);
-    PM_LAUNCHED("k_dqn_update_n");
-    return PM_OK;
+    return dqn_entry(DQN_UPDATE, d, true, o, ns, stream);
 }

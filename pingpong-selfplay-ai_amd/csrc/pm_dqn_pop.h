@@ -14,6 +14,14 @@ struct pm_dqn_member {
 };
 
 namespace pm {
+// pm_dqn.hip: pm_dqn's argument check, then pm_dqn_opt's (a null record is the defaults and passes).
+int dqn_check(const pm_dqn* d, const pm_dqn_opt* o);
+// pm_dqn.hip: one learner launch, its kernel chosen there and nowhere else. with_opt false: the plain kernels;
+// true: the _opt ones on *o (null = the defaults), or with a horizon buffer hz the _n ones (apply has none).
+// gate: DQN_UPDATE_GATED's, the launch does nothing when gate[0] < 0 (the sampler's mark of a void update).
+enum DqnStage { DQN_GRADS, DQN_APPLY, DQN_UPDATE, DQN_UPDATE_GATED };
+int dqn_launch(DqnStage stage, const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const uint8_t* hz,
+               const int64_t* gate, hipStream_t st);
 // pm_dqn_replay.hip: what pm_dqn_replay_update checks behind pm_dqn's and pm_dqn_opt's own checks.
 int dqn_replay_check(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updates);
 // One launch each, grid n. gated: the idx[0] < 0 gate of k_dqr_update_opt (the replay path).

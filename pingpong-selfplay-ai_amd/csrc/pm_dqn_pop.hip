@@ -61,9 +61,7 @@ int build_table(const char* who, const pm_dqn* d, const pm_dqn_opt* opt, const p
     PM_REQUIRE(d, PM_E_ARG, "%s: null descriptor array", who);
     tab.assign((size_t)n, pm_dqn_member{});
     for (int p = 0; p < n; ++p) {
-        if (int rc = pm::dqn_check(&d[p])) return pm::pop_member_fail(rc, who, p);
-        if (opt)
-            if (int rc = pm::dqn_check_opt(&opt[p])) return pm::pop_member_fail(rc, who, p);
+        if (int rc = pm::dqn_check(&d[p], opt ? &opt[p] : nullptr)) return pm::pop_member_fail(rc, who, p);
         if (rp) {
             if (int rc = pm::dqn_replay_check(&d[p], &rp[p], 1)) return pm::pop_member_fail(rc, who, p);
             PM_REQUIRE(rp[p].cap > 0, PM_E_SIZE, "%s: member %d: cap=%lld", who, p, (long long)rp[p].cap);

@@ -165,18 +165,21 @@ __global__ __launch_bounds__(kScatter) void k_dqp_scatter(const pm_dqn_member* t
 }
 
 // ----------------------------------------------------------------------------- pm_replay_push
-__global__ __launch_bounds__(256) void k_push_rows(float* __restrict__ trans, float* __restrict__ prios,
-                                                   float* __restrict__ leaf, int64_t cap, int64_t pos, float alpha,
-                                                   float prio, const float* __restrict__ s, const int32_t* __restrict__ act,
-                                                   const float* __restrict__ rew, const float* __restrict__ ns,
-                                                   const uint8_t* __restrict__ done, int n) {
+// k_push_rows' and k_push_rows_n's body. kHz: a horizon per row, (horizon - 1) & 7 into bits 16..18 of the last word.
+template <bool kHz>
+__device__ __forceinline__ void push_rows_body(float* __restrict__ trans, float* __restrict__ prios,
+                                               float* __restrict__ leaf, int64_t cap, int64_t pos, float alpha, float prio,
+                                               const float* __restrict__ s, const int32_t* __restrict__ act,
+                                               const float* __restrict__ rew, const float* __restrict__ ns,
+                                               const uint8_t* __restrict__ done, const uint8_t* __restrict__ hz, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int64_t slot = pos + i;
     if (slot >= cap) slot -= cap;  // pos < cap and i < n <= cap
     const float* a = s + (size_t)i * 7;
     const float* b = ns + (size_t)i * 7;
-    const int bits = (act[i] & 0xff) | ((done[i] ? 1 : 0) << 8);
+    int bits = (act[i] & 0xff) | ((done[i] ? 1 : 0) << 8);
+    if (kHz) bits |= ((hz[i] - 1) & 7) << 16;
     float4* row = reinterpret_cast<float4*>(trans + slot * PM_TRANS_F);
     row[0] = make_float4(a[0], a[1], a[2], a[3]);
     row[1] = make_float4(a[4], a[5], a[6], rew[i]);
@@ -186,27 +189,22 @@ __global__ __launch_bounds__(256) void k_push_rows(float* __restrict__ trans, fl
     leaf[slot] = prio_pow(prio, alpha);
 }
 
-// k_push_rows with a horizon per row (pm_replay_push_n): (horizon - 1) & 7 into bits 16..18 of the last word.
+__global__ __launch_bounds__(256) void k_push_rows(float* __restrict__ trans, float* __restrict__ prios,
+                                                   float* __restrict__ leaf, int64_t cap, int64_t pos, float alpha,
+                                                   float prio, const float* __restrict__ s, const int32_t* __restrict__ act,
+                                                   const float* __restrict__ rew, const float* __restrict__ ns,
+                                                   const uint8_t* __restrict__ done, int n) {
+    push_rows_body<false>(trans, prios, leaf, cap, pos, alpha, prio, s, act, rew, ns, done, nullptr, n);
+}
+
+// pm_replay_push_n
 __global__ __launch_bounds__(256) void k_push_rows_n(float* __restrict__ trans, float* __restrict__ prios,
                                                      float* __restrict__ leaf, int64_t cap, int64_t pos, float alpha,
                                                      float prio, const float* __restrict__ s, const int32_t* __restrict__ act,
                                                      const float* __restrict__ rew, const float* __restrict__ ns,
                                                      const uint8_t* __restrict__ done, const uint8_t* __restrict__ hz,
                                                      int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    int64_t slot = pos + i;
-    if (slot >= cap) slot -= cap;  // pos < cap and i < n <= cap
-    const float* a = s + (size_t)i * 7;
-    const float* b = ns + (size_t)i * 7;
-    const int bits = (act[i] & 0xff) | ((done[i] ? 1 : 0) << 8) | (((hz[i] - 1) & 7) << 16);
-    float4* row = reinterpret_cast<float4*>(trans + slot * PM_TRANS_F);
-    row[0] = make_float4(a[0], a[1], a[2], a[3]);
-    row[1] = make_float4(a[4], a[5], a[6], rew[i]);
-    row[2] = make_float4(b[0], b[1], b[2], b[3]);
-    row[3] = make_float4(b[4], b[5], b[6], __int_as_float(bits));
-    prios[slot] = prio;
-    leaf[slot] = prio_pow(prio, alpha);
+    push_rows_body<true>(trans, prios, leaf, cap, pos, alpha, prio, s, act, rew, ns, done, hz, n);
 }
 
 // The level-1 nodes overlapping the pushed ring range, four lanes each (k_per_subs's form).
@@ -249,13 +247,11 @@ int pm::dqn_replay_check(const pm_dqn* d, const pm_dqn_replay* rp, int32_t updat
 }
 
 int pm::dqp_launch_sample(const pm_dqn_member* tab, uint8_t* const* hzt, int n, int upd, hipStream_t st) {
-    if (hzt) {
+    if (hzt)
         hipLaunchKernelGGL(k_dqp_sample_n, dim3(n), dim3(256), 0, st, tab, hzt, upd);
-        PM_LAUNCHED("k_dqp_sample_n");
-        return PM_OK;
-    }
-    hipLaunchKernelGGL(k_dqp_sample, dim3(n), dim3(256), 0, st, tab, upd);
-    PM_LAUNCHED("k_dqp_sample");
+    else
+        hipLaunchKernelGGL(k_dqp_sample, dim3(n), dim3(256), 0, st, tab, upd);
+    PM_LAUNCHED(hzt ? "k_dqp_sample_n" : "k_dqp_sample");
     return PM_OK;
 }
 
@@ -265,28 +261,20 @@ int pm::dqp_launch_scatter(const pm_dqn_member* tab, int n, hipStream_t st) {
     return PM_OK;
 }
 
-// pm_dqn_replay_update (with_opt false: k_dqr_update in the middle), pm_dqn_replay_update_opt (k_dqr_update_opt) and
-// pm_dqn_replay_update_n (hz: k_dqr_sample_n and k_dqr_update_n).
+// pm_dqn_replay_update (with_opt false), pm_dqn_replay_update_opt and pm_dqn_replay_update_n (hz: k_dqr_sample_n); the
+// middle launch's kernel is dqn_launch's choice from the same three.
 static int replay_update(const pm_dqn* d, bool with_opt, const pm_dqn_opt* o, const pm_dqn_replay* rp, int32_t updates,
                          void* stream, uint8_t* hz = nullptr) {
-    if (int rc = dqn_check(d)) return rc;
-    if (with_opt)
-        if (int rc = dqn_check_opt(o)) return rc;
+    if (int rc = dqn_check(d, o)) return rc;
     if (int rc = dqn_replay_check(d, rp, updates)) return rc;
     hipStream_t st = pm_stream(stream);
     for (int k = 0; k < updates; ++k) {
-        if (hz) {
+        if (hz)
             hipLaunchKernelGGL(k_dqr_sample_n, dim3(1), dim3(256), 0, st, *d, *rp, k, hz);
-            PM_LAUNCHED("k_dqr_sample_n");
-            if (int rc = dqn_launch_update_gated_n(d, o, hz, rp->idx, st)) return rc;
-            hipLaunchKernelGGL(k_dqr_scatter, dim3(1), dim3(kScatter), 0, st, *d, *rp);
-            PM_LAUNCHED("k_dqr_scatter");
-            continue;
-        }
-        hipLaunchKernelGGL(k_dqr_sample, dim3(1), dim3(256), 0, st, *d, *rp, k);
-        PM_LAUNCHED("k_dqr_sample");
-        if (int rc = with_opt ? dqn_launch_update_gated_opt(d, o, rp->idx, st) : dqn_launch_update_gated(d, rp->idx, st))
-            return rc;
+        else
+            hipLaunchKernelGGL(k_dqr_sample, dim3(1), dim3(256), 0, st, *d, *rp, k);
+        PM_LAUNCHED(hz ? "k_dqr_sample_n" : "k_dqr_sample");
+        if (int rc = dqn_launch(DQN_UPDATE_GATED, d, with_opt, o, hz, rp->idx, st)) return rc;
         hipLaunchKernelGGL(k_dqr_scatter, dim3(1), dim3(kScatter), 0, st, *d, *rp);
         PM_LAUNCHED("k_dqr_scatter");
     }
@@ -326,15 +314,13 @@ static int replay_push(float* trans, float* prios, void* per_work, int64_t cap, 
         return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
     };
     // the leaves land (one launch) before the nodes over them are summed (the next), level 1 before level 2
-    if (hz) {
+    if (hz)
         hipLaunchKernelGGL(k_push_rows_n, dim3(pm_blocks(n, 256)), dim3(256), 0, st, trans, prios, tr.leaf, cap, pos, alpha,
                            prio, s, act, rew, ns, done, hz, (int)n);
-        PM_LAUNCHED("k_push_rows_n");
-    } else {
+    else
         hipLaunchKernelGGL(k_push_rows, dim3(pm_blocks(n, 256)), dim3(256), 0, st, trans, prios, tr.leaf, cap, pos, alpha,
                            prio, s, act, rew, ns, done, (int)n);
-        PM_LAUNCHED("k_push_rows");
-    }
+    PM_LAUNCHED(hz ? "k_push_rows_n" : "k_push_rows");
     hipLaunchKernelGGL(k_push_subs, dim3(grid(((int64_t)n / PER_SUB + 2) * 4)), dim3(256), 0, st, cap, pos, (int64_t)n, tr);
     PM_LAUNCHED("k_push_subs");
     hipLaunchKernelGGL(k_push_chunks, dim3(grid((int64_t)n / PER_CHUNK + 2)), dim3(256), 0, st, cap, pos, (int64_t)n, tr);

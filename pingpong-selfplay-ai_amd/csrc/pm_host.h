@@ -32,18 +32,6 @@ int pm_rnn_act_part(const float* w_opp, const int32_t* opp_id, int32_t n_opp, co
 
 static inline unsigned pm_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
-// pm_dqn.hip, for pm_dqn_replay.hip: the pm_dqn_* argument check, and k_dqn_update's two bodies in a launch
-// that does nothing when gate[0] < 0 (the sampler's mark of a void update).
-namespace pm {
-int dqn_check(const pm_dqn* d);
-int dqn_launch_update_gated(const pm_dqn* d, const int64_t* gate, hipStream_t st);
-// The same two with a pm_dqn_opt (null = the defaults): its check, and k_dqr_update_opt's launch.
-int dqn_check_opt(const pm_dqn_opt* o);
-int dqn_launch_update_gated_opt(const pm_dqn* d, const pm_dqn_opt* o, const int64_t* gate, hipStream_t st);
-int dqn_launch_update_gated_n(const pm_dqn* d, const pm_dqn_opt* o, const uint8_t* hz, const int64_t* gate,
-                              hipStream_t st);
-}  // namespace pm
-
 // Launch timing (pm_timer_arm / pm_timer_read, pm_api.cpp): an armed kernel's next launch goes
 // through hipExtLaunchKernel with the timer's events; every other launch is a plain one.
 bool pm_timer_take(int kernel, hipEvent_t* start, hipEvent_t* stop);

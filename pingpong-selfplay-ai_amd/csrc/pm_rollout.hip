@@ -407,19 +407,16 @@ static int rollout_launch(const pm_env_params* p, const pm_env_state* s, const f
     hipStream_t st = pm_stream(stream);
     hipLaunchKernelGGL(k_rollout_heads, dim3(steps), dim3(kHeadsBlock), 0, st, paramsB, seed_net, counter0, heads_ws);
     PM_LAUNCHED("k_rollout_heads");
-    if (rp && rn) {
-        pm_launch(PM_TIMER_ROLLOUT, k_rollout_push_n, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
-                  (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
-                  reinterpret_cast<long long*>(stats), n, *rp, *rn);
-        PM_LAUNCHED("k_rollout_push_n");
-        if (per_work) return per_launch_nodes(per_work, rp->cap, st);
-        return PM_OK;
-    }
-    if (rp) {
-        pm_launch(PM_TIMER_ROLLOUT, k_rollout_push, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
-                  (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
-                  reinterpret_cast<long long*>(stats), n, *rp);
-        PM_LAUNCHED("k_rollout_push");
+    if (rp) {  // two launches only because k_rollout_push_n takes the window as one argument more
+        if (rn)
+            pm_launch(PM_TIMER_ROLLOUT, k_rollout_push_n, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
+                      (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
+                      reinterpret_cast<long long*>(stats), n, *rp, *rn);
+        else
+            pm_launch(PM_TIMER_ROLLOUT, k_rollout_push, dim3(pm_blocks(n, 32)), dim3(kRollBlock), st, *p, *s, wA, wB,
+                      (const float*)heads_ws, (double)epsilon, seed_env, counter0, (int)steps, obsA, obsB,
+                      reinterpret_cast<long long*>(stats), n, *rp);
+        PM_LAUNCHED(rn ? "k_rollout_push_n" : "k_rollout_push");
         if (per_work) return per_launch_nodes(per_work, rp->cap, st);
         return PM_OK;
     }

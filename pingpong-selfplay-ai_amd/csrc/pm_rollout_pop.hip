@@ -135,7 +135,9 @@ __global__ __launch_bounds__(kRollBlock) __attribute__((amdgpu_waves_per_eu(3, 3
 }
 
 // k_rpp_push with the n-step window (k_rollout_push_n's body), member p's horizon and discount in rnt[p]; a member
-// with nstep 1 writes the one-step rows. Like the solo kernel it takes the compiler's own register budget.
+// with nstep 1 writes the one-step rows. Like the solo kernel it takes the compiler's own register budget. The
+// member-slicing prologue is k_rpp_push's, repeated on purpose: behind one rpp_push_body<kN> both kernels compiled
+// to different and longer text (2835 -> 2843 and 3955 -> 4012 instructions).
 __global__ __launch_bounds__(kRollBlock) void k_rpp_push_n(
     const pm_env_params p, const pm_env_state s, const pm_roll_member* __restrict__ tab,
     const RollN* __restrict__ rnt, int m, int tiles, uint64_t counter0, int steps, int64_t advance,
@@ -278,16 +280,14 @@ extern "C" int pm_rollout_pop_push(const pm_rollout_pop* pop, uint64_t counter0,
     }
     hipLaunchKernelGGL(k_rpp_heads, dim3(steps, n), dim3(kHeadsBlock), 0, st, (const pm_roll_member*)pop->tab, counter0);
     PM_LAUNCHED("k_rpp_heads");
-    if (pop->use_n) {
+    if (pop->use_n)
         pm_launch(PM_TIMER_ROLLOUT, k_rpp_push_n, dim3((unsigned)n * (unsigned)tiles), dim3(kRollBlock), st, pop->p,
                   pop->s, (const pm_roll_member*)pop->tab, (const RollN*)pop->rn, m, tiles, counter0, (int)steps,
                   advance, obsA, obsB);
-        PM_LAUNCHED("k_rpp_push_n");
-    } else {
+    else
         pm_launch(PM_TIMER_ROLLOUT, k_rpp_push, dim3((unsigned)n * (unsigned)tiles), dim3(kRollBlock), st, pop->p,
                   pop->s, (const pm_roll_member*)pop->tab, m, tiles, counter0, (int)steps, advance, obsA, obsB);
-        PM_LAUNCHED("k_rpp_push");
-    }
+    PM_LAUNCHED(pop->use_n ? "k_rpp_push_n" : "k_rpp_push");
     if (pop->node_blocks) {
         hipLaunchKernelGGL(k_rpp_nodes, dim3((unsigned)pop->node_blocks, n), dim3(256), 0, st,
                            (const pm_roll_member*)pop->tab);

@@ -93,7 +93,7 @@ __device__ __forceinline__ void store_hfeat(float* hfeat, int j, bool nxt, int l
     }
 }
 
-// Host functions called across the units (as dqn_check in pm_host.h).
+// Host functions called across the units (as dqn_check in pm_dqn_pop.h).
 namespace pm {
 int selfplay_check(const pm_selfplay* sp);                        // pm_selfplay.hip: every entry point's argument check
 int selfplay_launch_init(const pm_selfplay* sp, hipStream_t st);  // pm_sp_rollout.hip: k_sp_init

@@ -180,15 +180,17 @@ class DQNLearner:
         self.desc.isw = self.isw.data_ptr() if isw is not None else None
         self.desc.batch = n
 
-    def _call(self, name, stream=None):
-        if self.ns_desc is not None and name != "pm_dqn_apply":  # the apply step has no horizon
-            check(getattr(self.lib, name + "_n")(ctypes.byref(self.desc), ctypes.byref(self.opt) if self.opt else None,
-                                                 ctypes.byref(self.ns_desc), stream_ptr(stream)), name + "_n")
-        elif self.opt is None:
-            check(getattr(self.lib, name)(ctypes.byref(self.desc), stream_ptr(stream)), name)
-        else:
-            check(getattr(self.lib, name + "_opt")(ctypes.byref(self.desc), ctypes.byref(self.opt), stream_ptr(stream)),
-                  name + "_opt")
+    def _tier(self, base):
+        """The one place this learner's entry points are chosen: base's name and leading arguments with a horizon
+        buffer (_n), with options (_opt), or plain."""
+        d, o = ctypes.byref(self.desc), ctypes.byref(self.opt) if self.opt else None
+        if self.ns_desc is not None and base != "pm_dqn_apply":  # the apply step has no horizon
+            return base + "_n", (d, o, ctypes.byref(self.ns_desc))
+        return (base, (d,)) if o is None else (base + "_opt", (d, o))
+
+    def _call(self, base, stream=None, *tail):
+        name, args = self._tier(base)
+        check(getattr(self.lib, name)(*args, *tail, stream_ptr(stream)), name)
 
     def update(self, *batch, isw=None, horizon=None, stream=None):
         """One train_step; batch = (s, a, r, ns, done[, isw]) or nothing (buffers already filled).
@@ -222,16 +224,7 @@ class DQNLearner:
                             idx=self.idx.data_ptr(), u=u.data_ptr() if u is not None else None, cap=replay.cap,
                             size=replay.size, alpha=replay.alpha, beta_start=float(beta_start),
                             beta_frames=int(beta_frames), seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
-        if self.ns_desc is not None:
-            check(self.lib.pm_dqn_replay_update_n(ctypes.byref(self.desc), ctypes.byref(self.opt) if self.opt else None,
-                                                  ctypes.byref(self.ns_desc), ctypes.byref(rp), updates,
-                                                  stream_ptr(stream)), "pm_dqn_replay_update_n")
-        elif self.opt is None:
-            check(self.lib.pm_dqn_replay_update(ctypes.byref(self.desc), ctypes.byref(rp), updates, stream_ptr(stream)),
-                  "pm_dqn_replay_update")
-        else:
-            check(self.lib.pm_dqn_replay_update_opt(ctypes.byref(self.desc), ctypes.byref(self.opt), ctypes.byref(rp),
-                                                    updates, stream_ptr(stream)), "pm_dqn_replay_update_opt")
+        self._call("pm_dqn_replay_update", stream, ctypes.byref(rp), updates)
         replay.max_prio_stale = True
         return self.idx[:n], self.td[:n]
 

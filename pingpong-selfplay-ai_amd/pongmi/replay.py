@@ -111,15 +111,14 @@ class DeviceReplay:
             if lo < 1 or hi > _lib.PM_NSTEP_MAX:
                 raise ValueError(f"DeviceReplay.push: horizons must be 1..{_lib.PM_NSTEP_MAX}")
             horizon = horizon.to(device=dev, dtype=torch.uint8).contiguous()
-        prio = self.push_prio()
-        if horizon is None:
-            check(_lib.load().pm_replay_push(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos,
-                                             self.alpha, prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done), n,
-                                             stream_ptr(stream)), "pm_replay_push")
-        else:
-            check(_lib.load().pm_replay_push_n(ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos,
-                                               self.alpha, prio, ptr(s), ptr(a), ptr(r), ptr(ns), ptr(done),
-                                               ptr(horizon), n, stream_ptr(stream)), "pm_replay_push_n")
+        name = "pm_replay_push"
+        args = [ptr(self.trans), ptr(self.prios), ptr(self.work), self.cap, self.pos, self.alpha, self.push_prio(), ptr(s),
+                ptr(a), ptr(r), ptr(ns), ptr(done)]
+        if horizon is not None:  # the _n entry takes the horizons behind done
+            name += "_n"
+            args.append(ptr(horizon))
+        check(getattr(_lib.load(), name)(*args, n, stream_ptr(stream)), name)
+        if horizon is not None:
             self.max_horizon = max(self.max_horizon, hi)
         if self.size == 0:
             self.max_prio = 1.0

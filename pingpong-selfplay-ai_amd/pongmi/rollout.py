@@ -119,11 +119,11 @@ class SelfPlayRollout:
         args = (ctypes_ref(env.params), ctypes_ref(env.state), ptr(self.wA), ptr(self.wB), ptr(self.paramsB),
                 self.epsilon, env.seed, self.seed_net, env.counter, steps, ptr(self.heads), ptr(env.obsA),
                 ptr(env.obsB), ctypes_ref(rp), ptr(self.stats), env.n)
-        if nstep is None:
-            check(self.lib.pm_rollout_push(*args, stream_ptr()), "pm_rollout_push")
-        else:
-            check(self.lib.pm_rollout_push_n(*args, int(nstep), float(gamma), stream_ptr()), "pm_rollout_push_n")
-            replay.max_horizon = max(replay.max_horizon, int(nstep))
+        more = () if nstep is None else (int(nstep), float(gamma))  # what the _n entry takes behind n
+        name = "pm_rollout_push_n" if more else "pm_rollout_push"
+        check(getattr(self.lib, name)(*args, *more, stream_ptr()), name)
+        if more:
+            replay.max_horizon = max(replay.max_horizon, more[0])
         if steps and env.n:
             if replay.size == 0:
                 replay.max_prio = 1.0
